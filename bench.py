@@ -15,10 +15,16 @@ row ranges and each half ends with an RCCL all-gather of the solved factors (str
 scaling: total work fixed).  A rank count that does not match --gpus, or more ranks than
 visible GPUs, fails with a non-zero exit.
 
-The CPU baseline (rank 0, N=1) is one full epoch of the reference-structure port on the box's
-CPU share (BASELINE.md CPU-baseline plan: "C3 and C5: time >= 1 full epoch"); when the time
-guard predicts that the epoch would not finish inside the run's time limit it falls back to
-the sampled estimate and says so.
+A plain run sets up, warms up, times the steps and prints the line (with the roofline figures
+the library's event accounting of those same steps gives).  `--dump-outputs DIR` also writes
+what the last timed step left (the factors, as a fixed seeded row sample when they are large,
+and the losses the step returned) as DIR/<name>.npy.  `--full` adds the legs that take runs
+of their own: the parity check against the oracle and the CPU baseline.
+
+The CPU baseline (`--full`; rank 0, N=1) is one full epoch of the reference-structure port on
+the host's CPU share (BASELINE.md CPU-baseline plan: "C3 and C5: time >= 1 full epoch"); when
+the time guard predicts that the epoch would not finish inside the run's time limit it falls
+back to the sampled estimate and says so.
 
 Prints ONE JSON line on rank 0.
 """
@@ -63,6 +69,34 @@ PEAK_ATOMIC_GBS = 1300.0  # chip-wide float atomic adds (MI355X_MICROARCH.md, me
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+# --dump-outputs: bytes of one factor matrix's file (two matrices and the losses stay well
+# under 64 MB in all)
+DUMP_MATRIX_BYTES = 24 << 20
+
+
+def dump_rows(n, k, seed):
+    """The rows of an n × k factor matrix that --dump-outputs writes: every row when the
+    matrix fits into DUMP_MATRIX_BYTES as float64, else a fixed sample (sorted, drawn from
+    `seed` alone, so two builds write the same rows)."""
+    m = DUMP_MATRIX_BYTES // (k * 8)
+    if n <= m:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, m, replace=False))
+
+
+def dump_outputs(outdir, ctx, seed, **losses):
+    """Writes what the last timed step left: user_factors.npy / item_factors.npy (float64,
+    the rows of dump_rows) and one float64 array per keyword (the losses the step returned)."""
+    os.makedirs(outdir, exist_ok=True)
+    for side, name in ((0, "user_factors"), (1, "item_factors")):
+        F = ctx.factors(side)
+        np.save(os.path.join(outdir, name + ".npy"), F[dump_rows(F.shape[0], F.shape[1], seed + side)])
+        del F
+    for name, v in losses.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.atleast_1d(np.asarray(v, np.float64)))
+    log("outputs of the last timed step written to %s" % outdir)
 
 
 MKL = "/opt/conda/lib/libmkl_rt.so.1"
@@ -331,6 +365,8 @@ def bench_bpr(args, rank, world):
     el = time.perf_counter() - t1
     log("c4: %d timed epochs in %.3fs" % (args.steps, el))
     st = ctx.solve_stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, seed, eval_loss=loss)
     upd = nnz * num_neg * args.steps
     sec = st["ms"] / 1e3 / max(st["launches"], 1)
     by = st["bytes"] / max(st["launches"], 1)
@@ -447,7 +483,8 @@ def bench_c1(args, rank):
     d = np.load(os.path.join(ROOT, "tests", "golden", "ml100k_shape.npz"))
     users, items = d["users"].astype(np.int64), d["items"].astype(np.int64)
     values = d["values"].astype(np.float64)
-    init = d["init_e9"].astype(np.float64) / 1e9
+    init = np.load(os.path.join(ROOT, "tests", "golden", "ml100k_init.npz"))["init_e9"]
+    init = init.astype(np.float64) / 1e9
     nu0, ni0, nnz0, k, seed = CONFIGS["c1"]
     ctx = qmf_amd.Context(k, args.precision, device=int(os.environ.get("LOCAL_RANK", "0")))
     ctx.group_signals(users, items, values)
@@ -478,6 +515,8 @@ def bench_c1(args, rank):
                                {sd: int(sum(ctx.row_classes(sd)["whitened"])) for sd in (0, 1)})
     roof = roofline_object(classes)
     roof["classes"] = classes
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, seed, epoch_losses=losses)
     out = {
         "metric": "WALS solves/sec and ms/epoch at k=%d; achieved fraction of HBM roofline" % k,
         "value": round(solves / el, 1), "unit": "solves/s", "n_gpus": 1, "steps": args.steps,
@@ -720,6 +759,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--precision", type=int, default=64, choices=(32, 64))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left (factors, losses) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the parity check against the oracle and "
+                         "the CPU baseline (the options below choose among them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline", default="epoch", choices=("sample", "epoch", "none"))
     ap.add_argument("--no-parity", action="store_true")
@@ -727,10 +772,14 @@ def main():
     ap.add_argument("--allow-variant", action="store_true",
                     help="measure a timing-variant library (QMFX_LIB); the line is marked")
     args = ap.parse_args()
-    if args.no_cpu_baseline:
+    if args.no_cpu_baseline or not args.full:
         args.cpu_baseline = "none"
+    if not args.full:
+        args.no_parity = True
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     # N ranks: relaunch under torch.distributed.run as a CHILD process before anything
     # touches the GPU (this process never initialises HIP), and exit with its status
@@ -750,7 +799,8 @@ def main():
     variant = qmf_amd._abi.build_variant()
     check_env(os.environ, variant, args.allow_variant)
     check_world(args.gpus, world, qmf_amd.device_count(), local)
-    cpu_share()
+    if args.full:
+        cpu_share()
     if args.config == "c1":
         return bench_c1(args, rank)
     if args.config in BPR_CONFIGS:
@@ -839,6 +889,9 @@ def main():
     hbm_frac_epoch = epoch_bytes / (ms_epoch / 1e3) / (PEAK_HBM_GBS * 1e9)
     if rank != 0:
         return
+    if args.dump_outputs:
+        # every rank holds the whole of both factor matrices after a half's all-gather
+        dump_outputs(args.dump_outputs, ctx, seed, loss=loss)
     out = {
         "metric": "WALS solves/sec and ms/epoch at k=%d; achieved fraction of HBM roofline" % k,
         "value": round(value, 1),
@@ -867,7 +920,8 @@ def main():
         out["variant"] = variant
     if xfields is not None:
         out["exchange"] = xfields
-    nthreads, host = cpu_share()
+    if args.full:
+        nthreads, host = cpu_share()
     if not args.no_parity and world == 1:
         t0 = time.perf_counter()
         out["parity"] = parity_check(ctx, CONFIGS[args.config], nthreads, args.precision)

@@ -11,6 +11,7 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 def load_ml100k():
     z = np.load(os.path.join(GOLDEN, "ml100k_shape.npz"))
     d = {k: z[k] for k in z.files}
+    d["init_e9"] = np.load(os.path.join(GOLDEN, "ml100k_init.npz"))["init_e9"]
     d["users"] = d["users"].astype(np.int64)
     d["items"] = d["items"].astype(np.int64)
     d["values"] = d["values"].astype(np.float64)

@@ -82,6 +82,36 @@ def test_product_library_is_not_a_variant():
     assert qmf_amd._abi.build_variant() == ""
 
 
+def test_dump_rows_are_a_fixed_sample_within_the_size_bound():
+    """--dump-outputs: a small matrix is written whole; of C3's user factors (10M × 128) a
+    sorted sample without repeats that depends on the seed alone and stays within the bound."""
+    import numpy as np
+    assert np.array_equal(bench.dump_rows(1682, 30, 7), np.arange(1682))
+    r = bench.dump_rows(10_000_000, 128, 3)
+    assert np.array_equal(r, bench.dump_rows(10_000_000, 128, 3))
+    assert not np.array_equal(r, bench.dump_rows(10_000_000, 128, 4))
+    assert len(r) * 128 * 8 <= bench.DUMP_MATRIX_BYTES < len(r) * 128 * 8 + 128 * 8
+    assert np.all(np.diff(r) > 0) and r[0] >= 0 and r[-1] < 10_000_000
+    # two matrices and the losses: under 64 MB in all, whatever k
+    assert all(2 * len(bench.dump_rows(10_000_000, k, 3)) * k * 8 < (64 << 20) - 4096
+               for k in (30, 64, 128, 256))
+
+
+def test_dump_outputs_writes_float64_npy(tmp_path):
+    import numpy as np
+
+    class Ctx:  # the part of qmf_amd.Context that dump_outputs uses
+        def factors(self, side):
+            return np.arange((5 + side) * 4, dtype=np.float64).reshape(5 + side, 4)
+    out = tmp_path / "nested" / "dump"
+    bench.dump_outputs(str(out), Ctx(), 3, loss=1.5, epoch_losses=[2.0, 1.0])
+    got = {p.name: np.load(p) for p in out.iterdir()}
+    assert set(got) == {"user_factors.npy", "item_factors.npy", "loss.npy", "epoch_losses.npy"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["item_factors.npy"], Ctx().factors(1))
+    assert got["loss.npy"].tolist() == [1.5] and got["epoch_losses.npy"].tolist() == [2.0, 1.0]
+
+
 def _exchange_rank(rank, world, port, q):
     import torch
     import torch.distributed as dist

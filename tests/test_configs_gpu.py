@@ -10,7 +10,7 @@ size (whitened user rows, direct or multi-wave item rows; fp32 split-bf16 Gram a
 * C4 (BPR, k=64): the exact update sequence of a serial epoch at k=64, and the Hogwild
   epoch's eval-loss trajectory against a serial reference SGD on a C4-shaped matrix.
 
-The full-size C3 matrix is checked inside bench.py (sampled rows re-solved by the oracle
+The full-size C3 matrix is checked by `bench.py --full` (sampled rows re-solved by the oracle
 against the device's own fixed side; `parity` in the BENCH line)."""
 import os
 

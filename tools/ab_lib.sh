@@ -10,7 +10,7 @@ for lib in "$@"; do
   i=$((i+1))
   if [ "$lib" = prod ]; then unset QMFX_LIB; else export QMFX_LIB=$lib; fi
   timeout -k 10 ${LIMIT:-300} python3 -u bench.py --config ${CFG:-c5} --precision ${PREC:-64} \
-    --steps ${STEPS:-2} --warmup ${WARM:-1} --cpu-baseline none ${NOPARITY:+--no-parity} --allow-variant \
+    --steps ${STEPS:-2} --warmup ${WARM:-1} --full --cpu-baseline none ${NOPARITY:+--no-parity} --allow-variant \
     > gpurun_out/ab/$i.json 2> gpurun_out/ab/$i.err || { echo "bench failed: $lib"; tail -5 gpurun_out/ab/$i.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('gpurun_out/ab/$i.json')); r=d['roofline']

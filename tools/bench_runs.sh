@@ -12,7 +12,7 @@ for spec in "$@"; do
   steps=${steps:-5}; warm=${warm:-2}
   echo "== $cfg fp$prec steps=$steps warmup=$warm"
   timeout -k 10 ${LIMIT:-400} python3 -u bench.py --config "$cfg" --precision "$prec" --steps "$steps" \
-    --warmup "$warm" --cpu-baseline none ${EXTRA:-} > "$OUT/${cfg}_${prec}.json" 2> "$OUT/${cfg}_${prec}.err"
+    --warmup "$warm" --full --cpu-baseline none ${EXTRA:-} > "$OUT/${cfg}_${prec}.json" 2> "$OUT/${cfg}_${prec}.err"
   rc=$?
   tail -3 "$OUT/${cfg}_${prec}.err"
   if [ $rc -ne 0 ]; then echo "FAILED rc=$rc"; exit $rc; fi

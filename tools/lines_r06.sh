@@ -7,7 +7,7 @@ OUT=gpurun_out/lines
 mkdir -p "$OUT"
 line() {  # name, limit, bench args...
   local name=$1 lim=$2; shift 2
-  timeout -k 10 "$lim" python3 -u bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" \
+  timeout -k 10 "$lim" python3 -u bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" \
     || { echo "$name FAILED"; tail -5 "$OUT/$name.err"; exit 1; }
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[2], d['ms_per_step'], 'ms/step', d['value'], d['unit'], r['kernel'], r['frac'], 'cpu', (d.get('cpu_baseline') or {}).get('value'), 'parity', (d.get('parity') or {}).get('pass'))" "$OUT/$name.json" "$name"
 }
