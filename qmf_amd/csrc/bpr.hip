@@ -421,38 +421,38 @@ static hipError_t bpr_eval(const T* U, const T* I, const T* bias, const int64_t*
   return hipGetLastError();
 }
 
-hipError_t launch_bpr_epoch_f32(const BprArgs<float>& a, int kp, hipStream_t s) {
+hipError_t launch_bpr_epoch(const BprArgs<float>& a, int kp, hipStream_t s) {
 #define CALL(E) bpr_epoch<float, E>(a, s)
   QMFX_E_SWITCH(kp, CALL)
 #undef CALL
 }
-hipError_t launch_bpr_epoch_f64(const BprArgs<double>& a, int kp, hipStream_t s) {
+hipError_t launch_bpr_epoch(const BprArgs<double>& a, int kp, hipStream_t s) {
 #define CALL(E) bpr_epoch<double, E>(a, s)
   QMFX_E_SWITCH(kp, CALL)
 #undef CALL
 }
-hipError_t launch_bpr_apply_f32(const BprArgs<float>& a, const int64_t* trip, int64_t n, int kp,
-                                hipStream_t s) {
+hipError_t launch_bpr_apply(const BprArgs<float>& a, const int64_t* trip, int64_t n, int kp,
+                            hipStream_t s) {
 #define CALL(E) bpr_apply<float, E>(a, trip, n, s)
   QMFX_E_SWITCH(kp, CALL)
 #undef CALL
 }
-hipError_t launch_bpr_apply_f64(const BprArgs<double>& a, const int64_t* trip, int64_t n,
-                                int kp, hipStream_t s) {
+hipError_t launch_bpr_apply(const BprArgs<double>& a, const int64_t* trip, int64_t n,
+                            int kp, hipStream_t s) {
 #define CALL(E) bpr_apply<double, E>(a, trip, n, s)
   QMFX_E_SWITCH(kp, CALL)
 #undef CALL
 }
-hipError_t launch_bpr_eval_f32(const float* U, const float* I, const float* bias,
-                               const int64_t* trip, int64_t n, int kp, int use_biases,
-                               double* partial, double* out, hipStream_t s) {
+hipError_t launch_bpr_eval(const float* U, const float* I, const float* bias,
+                           const int64_t* trip, int64_t n, int kp, int use_biases,
+                           double* partial, double* out, hipStream_t s) {
 #define CALL(NT) bpr_eval<float, NT>(U, I, bias, trip, n, kp, use_biases, partial, out, s)
   QMFX_NT_SWITCH(kp, CALL)
 #undef CALL
 }
-hipError_t launch_bpr_eval_f64(const double* U, const double* I, const double* bias,
-                               const int64_t* trip, int64_t n, int kp, int use_biases,
-                               double* partial, double* out, hipStream_t s) {
+hipError_t launch_bpr_eval(const double* U, const double* I, const double* bias,
+                           const int64_t* trip, int64_t n, int kp, int use_biases,
+                           double* partial, double* out, hipStream_t s) {
 #define CALL(NT) bpr_eval<double, NT>(U, I, bias, trip, n, kp, use_biases, partial, out, s)
   QMFX_NT_SWITCH(kp, CALL)
 #undef CALL

@@ -163,15 +163,15 @@ hipError_t launch_synth_values_any(const uint64_t* keys, int64_t n, uint64_t div
                     : synth_values<double>(keys, n, div, nitems, user_major, seed, (double*)val, s);
 }
 
-hipError_t launch_fill_uniform_f32(float* X, int64_t n, int kp, int k, double bound,
-                                   uint64_t seed, hipStream_t s) {
+hipError_t launch_fill_uniform(float* X, int64_t n, int kp, int k, double bound,
+                               uint64_t seed, hipStream_t s) {
   if (n > 0)
     hipLaunchKernelGGL(fill_uniform_kernel<float>, dim3(nb(n * kp)), dim3(256), 0, s, X, n, kp, k,
                        bound, seed);
   return hipGetLastError();
 }
-hipError_t launch_fill_uniform_f64(double* X, int64_t n, int kp, int k, double bound,
-                                   uint64_t seed, hipStream_t s) {
+hipError_t launch_fill_uniform(double* X, int64_t n, int kp, int k, double bound,
+                               uint64_t seed, hipStream_t s) {
   if (n > 0)
     hipLaunchKernelGGL(fill_uniform_kernel<double>, dim3(nb(n * kp)), dim3(256), 0, s, X, n, kp,
                        k, bound, seed);

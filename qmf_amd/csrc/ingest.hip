@@ -116,12 +116,12 @@ struct DevTmp {  // hipcub temporary storage, grown on demand
   } while (0)
 
 // distinct ids of `id` (ascending, signed order) → *table (allocated here, ≥ *m entries)
-hipError_t distinct_ids(const int64_t* id, int64_t n, int64_t** table, int64_t* m, DevTmp& tmp,
-                        hipStream_t s) {
-  int64_t *sorted = nullptr, *uniq = nullptr;
+hipError_t distinct_ids(const int64_t* id, int64_t n, DevPtr<int64_t>& table, int64_t* m,
+                        DevTmp& tmp, hipStream_t s) {
+  int64_t* sorted = nullptr;
   IGCHK(hipMalloc(&sorted, (size_t)n * 8));
-  IGCHK(hipMalloc(&uniq, (size_t)n * 8 + 16));
-  *table = uniq;  // owned by the caller from here on
+  IGCHK(dev_alloc(table, (size_t)n * 8 + 16));
+  int64_t* uniq = table;
   int64_t* d_num = uniq + n;
   size_t t1 = 0, t2 = 0;
   IGCHK(hipcub::DeviceRadixSort::SortKeys(nullptr, t1, id, sorted, (int)n, 0, 64, s));
@@ -180,8 +180,8 @@ hipError_t group_records_t(const void* d_records, int64_t n, IngestOut& o, hipSt
   hipLaunchKernelGGL((unpack_records_kernel<T>), dim3(nblk(n)), dim3(256), 0, s,
                      (const uint64_t*)d_records, n, uid, iid, val);
   IGCHK(hipGetLastError());
-  IGCHK(distinct_ids(uid, n, &o.ids[0], &o.n[0], tmp, s));
-  IGCHK(distinct_ids(iid, n, &o.ids[1], &o.n[1], tmp, s));
+  IGCHK(distinct_ids(uid, n, o.ids[0], &o.n[0], tmp, s));
+  IGCHK(distinct_ids(iid, n, o.ids[1], &o.n[1], tmp, s));
   if (o.n[0] > 0x7fffffffll || o.n[1] > 0x7fffffffll) return hipErrorInvalidValue;
   int32_t *uidx = nullptr, *iidx = nullptr;
   IGCHK(hipMalloc(&uidx, (size_t)n * 4));
@@ -193,12 +193,12 @@ hipError_t group_records_t(const void* d_records, int64_t n, IngestOut& o, hipSt
   (void)hipFree(uid);
   (void)hipFree(iid);
   for (int side = 0; side < 2; ++side) {
-    IGCHK(hipMalloc(&o.rowptr[side], (size_t)(o.n[side] + 1) * 8));
-    IGCHK(hipMalloc(&o.col[side], (size_t)n * 4));
-    IGCHK(hipMalloc(&o.val[side], (size_t)n * sizeof(T)));
+    IGCHK(dev_alloc(o.rowptr[side], (size_t)(o.n[side] + 1) * 8));
+    IGCHK(dev_alloc(o.col[side], (size_t)n * 4));
+    IGCHK(dev_alloc(o.val[side], (size_t)n * sizeof(T)));
   }
-  IGCHK(orient<T>(uidx, iidx, val, n, o.n[0], o.rowptr[0], o.col[0], (T*)o.val[0], tmp, s));
-  IGCHK(orient<T>(iidx, uidx, val, n, o.n[1], o.rowptr[1], o.col[1], (T*)o.val[1], tmp, s));
+  IGCHK(orient<T>(uidx, iidx, val, n, o.n[0], o.rowptr[0], o.col[0], o.val[0].as<T>(), tmp, s));
+  IGCHK(orient<T>(iidx, uidx, val, n, o.n[1], o.rowptr[1], o.col[1], o.val[1].as<T>(), tmp, s));
   (void)hipFree(uidx);
   (void)hipFree(iidx);
   (void)hipFree(val);

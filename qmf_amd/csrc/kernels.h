@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "own.h"
+
 namespace qmfx {
 
 // Per-slot row descriptor of a side's processing order (built once with the buckets):
@@ -102,12 +104,13 @@ hipError_t launch_gram_big(const double* Y, int64_t n, int nt, double* G, double
 constexpr int kMaxNTN = 8;
 hipError_t launch_wals_woodbury(const SolveArgs<float>& a, int nt, int ntn, hipStream_t s);
 hipError_t launch_wals_woodbury(const SolveArgs<double>& a, int nt, int ntn, hipStream_t s);
+// cus: compute units of the device (sizes the persistent grid)
 hipError_t launch_whiten(const float* in, float* out, const int64_t* order, int64_t nrows,
                          int nt, const float* Linv, double* rowloss, double lambda,
-                         bool unwhiten, hipStream_t s);
+                         bool unwhiten, int cus, hipStream_t s);
 hipError_t launch_whiten(const double* in, double* out, const int64_t* order, int64_t nrows,
                          int nt, const double* Linv, double* rowloss, double lambda,
-                         bool unwhiten, hipStream_t s);
+                         bool unwhiten, int cus, hipStream_t s);
 // scratch: KP·(KP+1) doubles, used when KP > 128 (the fp64 matrix does not fit LDS)
 hipError_t launch_chol_inv(const float* G, int nt, int k, double lambda, float* Linv,
                            int32_t* status, double* scratch, hipStream_t s);
@@ -118,9 +121,9 @@ hipError_t launch_gram(const float* Y, int64_t n, int nt, float* G, double* part
 hipError_t launch_gram(const double* Y, int64_t n, int nt, double* G, double* partial,
                        int max_blocks, hipStream_t s);
 hipError_t launch_sum_f64(const double* x, int64_t n, double* out, hipStream_t s);
-hipError_t launch_mfma_selftest_f32(const float* A, const float* B, float* C, hipStream_t s);
-hipError_t launch_mfma_selftest_f64(const double* A, const double* B, double* C,
-                                    hipStream_t s);
+hipError_t launch_mfma_selftest(const float* A, const float* B, float* C, hipStream_t s);
+hipError_t launch_mfma_selftest(const double* A, const double* B, double* C,
+                                hipStream_t s);
 
 // Pivoted fp64 re-solve of the rows flagged in `status` (fallback.hip)
 template <typename T>
@@ -176,18 +179,18 @@ struct BprArgs {
   int atomic_user;         // 1: add the user row's net change atomically (heavy users)
 };
 
-hipError_t launch_bpr_epoch_f32(const BprArgs<float>& a, int kp, hipStream_t s);
-hipError_t launch_bpr_epoch_f64(const BprArgs<double>& a, int kp, hipStream_t s);
-hipError_t launch_bpr_apply_f32(const BprArgs<float>& a, const int64_t* trip, int64_t n,
-                                int kp, hipStream_t s);
-hipError_t launch_bpr_apply_f64(const BprArgs<double>& a, const int64_t* trip, int64_t n,
-                                int kp, hipStream_t s);
-hipError_t launch_bpr_eval_f32(const float* U, const float* I, const float* bias,
-                               const int64_t* trip, int64_t n, int kp, int use_biases,
-                               double* partial, double* out, hipStream_t s);
-hipError_t launch_bpr_eval_f64(const double* U, const double* I, const double* bias,
-                               const int64_t* trip, int64_t n, int kp, int use_biases,
-                               double* partial, double* out, hipStream_t s);
+hipError_t launch_bpr_epoch(const BprArgs<float>& a, int kp, hipStream_t s);
+hipError_t launch_bpr_epoch(const BprArgs<double>& a, int kp, hipStream_t s);
+hipError_t launch_bpr_apply(const BprArgs<float>& a, const int64_t* trip, int64_t n,
+                            int kp, hipStream_t s);
+hipError_t launch_bpr_apply(const BprArgs<double>& a, const int64_t* trip, int64_t n,
+                            int kp, hipStream_t s);
+hipError_t launch_bpr_eval(const float* U, const float* I, const float* bias,
+                           const int64_t* trip, int64_t n, int kp, int use_biases,
+                           double* partial, double* out, hipStream_t s);
+hipError_t launch_bpr_eval(const double* U, const double* I, const double* bias,
+                           const int64_t* trip, int64_t n, int kp, int use_biases,
+                           double* partial, double* out, hipStream_t s);
 
 // Synthetic data + CSR build (data.hip)
 hipError_t launch_synth_keys(uint64_t* keys, int64_t n, uint64_t space, uint64_t seed,
@@ -210,19 +213,19 @@ hipError_t sort_keys(uint64_t* keys, uint64_t* scratch, int64_t n, int end_bit, 
 // the device → ascending id tables and both CSR orientations (buffers allocated by the
 // callee, owned by the caller; val in the context precision).
 struct IngestOut {
-  int64_t n[2] = {0, 0};                 // distinct users, items
-  int64_t* ids[2] = {nullptr, nullptr};  // ascending ids
-  int64_t* rowptr[2] = {nullptr, nullptr};
-  int32_t* col[2] = {nullptr, nullptr};
-  void* val[2] = {nullptr, nullptr};
+  int64_t n[2] = {0, 0};   // distinct users, items
+  DevPtr<int64_t> ids[2];  // ascending ids
+  DevPtr<int64_t> rowptr[2];
+  DevPtr<int32_t> col[2];
+  DevPtr<void> val[2];
 };
 hipError_t group_records(const void* d_records, int64_t n, int prec, IngestOut& out,
                          hipStream_t s);
 
-hipError_t launch_fill_uniform_f32(float* X, int64_t n, int kp, int k, double bound,
-                                   uint64_t seed, hipStream_t s);
-hipError_t launch_fill_uniform_f64(double* X, int64_t n, int kp, int k, double bound,
-                                   uint64_t seed, hipStream_t s);
+hipError_t launch_fill_uniform(float* X, int64_t n, int kp, int k, double bound,
+                               uint64_t seed, hipStream_t s);
+hipError_t launch_fill_uniform(double* X, int64_t n, int kp, int k, double bound,
+                               uint64_t seed, hipStream_t s);
 
 // Test-set ranking statistics (eval.hip)
 template <typename T>

@@ -225,12 +225,12 @@ hipError_t launch_sum_f64(const double* x, int64_t n, double* out, hipStream_t s
   return hipGetLastError();
 }
 
-hipError_t launch_mfma_selftest_f32(const float* A, const float* B, float* C, hipStream_t s) {
+hipError_t launch_mfma_selftest(const float* A, const float* B, float* C, hipStream_t s) {
   hipLaunchKernelGGL(mfma_selftest_kernel<float>, dim3(1), dim3(64), 0, s, A, B, C);
   return hipGetLastError();
 }
-hipError_t launch_mfma_selftest_f64(const double* A, const double* B, double* C,
-                                    hipStream_t s) {
+hipError_t launch_mfma_selftest(const double* A, const double* B, double* C,
+                                hipStream_t s) {
   hipLaunchKernelGGL(mfma_selftest_kernel<double>, dim3(1), dim3(64), 0, s, A, B, C);
   return hipGetLastError();
 }

@@ -1374,7 +1374,7 @@ hipError_t launch_heavy_reduce_big(double* part, double* partb, double* partc, c
 #define QMFX_BIG_SWITCH(NTV, CALL) return NTV == 16 ? CALL(16) : hipErrorInvalidValue;
 #define QMFX_BIG_ROW_SWITCH(NTV, CALL) return NTV == 16 ? CALL(16) : hipErrorInvalidValue;
 #else
-// the row kernel takes k > 128 only (qmfx.cpp use_big_rows); the tiled YᵀY also fp64 k = 80..128
+// the row kernel takes k > 128 only (ctx.h use_big_rows); the tiled YᵀY also fp64 k = 80..128
 #define QMFX_BIG_ROW_SWITCH(NTV, CALL)    \
   switch (NTV) {                          \
     case 9: return CALL(9);               \

@@ -1323,13 +1323,10 @@ static hipError_t launch_woodbury_st64_ntk(const SolveArgs<double>& a, int ntn, 
 template <typename T, int NT>
 static hipError_t launch_whiten_nt(const T* in, T* out, const int64_t* order, int64_t nrows,
                                    const T* Linv, double* rowloss, double lambda, bool unwhiten,
-                                   hipStream_t s) {
+                                   int cus, hipStream_t s) {
   if (nrows <= 0) return hipSuccess;
   if constexpr (WhitenLds<T, NT>::FITS) {
-    int dev = 0, cus = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (e != hipSuccess) return e;
+    if (cus <= 0) return hipErrorInvalidValue;
     const int64_t need = (nrows + 8 * 16 * QMFX_WHITEN_LDS_RG - 1) / (8 * 16 * QMFX_WHITEN_LDS_RG);
     int64_t cap = (int64_t)cus * WhitenLds<T, NT>::PER_CU;
     // test hook (read per launch): fewer workgroups, so that every wave strides over several
@@ -1366,6 +1363,7 @@ __global__ __launch_bounds__(1024) void chol_inv_global_kernel(const T* G, int k
                                                                double* A) {
   constexpr int KP = 16 * NT;
   constexpr int LD = KP + 1;
+  static_assert(4 * KP <= 1024, "the inverse gives each of the KP columns 4 of the 1024 threads");
   __shared__ double dinv[KP];
   const int tid = threadIdx.x;
   for (int idx = tid; idx < KP * KP; idx += 1024) {
@@ -1459,15 +1457,17 @@ hipError_t launch_wals_woodbury(const SolveArgs<double>& a, int nt, int ntn, hip
 }
 hipError_t launch_whiten(const float* in, float* out, const int64_t* order, int64_t nrows,
                          int nt, const float* Linv, double* rowloss, double lambda,
-                         bool unwhiten, hipStream_t s) {
-#define CALL(N) launch_whiten_nt<float, N>(in, out, order, nrows, Linv, rowloss, lambda, unwhiten, s)
+                         bool unwhiten, int cus, hipStream_t s) {
+#define CALL(N) \
+  launch_whiten_nt<float, N>(in, out, order, nrows, Linv, rowloss, lambda, unwhiten, cus, s)
   QMFX_NT_SWITCH_W(nt, CALL)
 #undef CALL
 }
 hipError_t launch_whiten(const double* in, double* out, const int64_t* order, int64_t nrows,
                          int nt, const double* Linv, double* rowloss, double lambda,
-                         bool unwhiten, hipStream_t s) {
-#define CALL(N) launch_whiten_nt<double, N>(in, out, order, nrows, Linv, rowloss, lambda, unwhiten, s)
+                         bool unwhiten, int cus, hipStream_t s) {
+#define CALL(N) \
+  launch_whiten_nt<double, N>(in, out, order, nrows, Linv, rowloss, lambda, unwhiten, cus, s)
   QMFX_NT_SWITCH_W(nt, CALL)
 #undef CALL
 }

@@ -115,7 +115,7 @@ def test_bpr_epoch_single_wave_exact(precision, tol, use_biases, num_neg, atomic
 def test_bpr_atomic_user_follows_user_skew(skewed):
     """The user row is stored plainly while concurrent waves rarely hold the same user; a
     dataset with one dominant user (≥ 1% of the positives per concurrent wave) switches it to
-    the atomic add (qmfx.cpp bpr_args)."""
+    the atomic add (api_bpr.cpp bpr_args)."""
     rng = np.random.default_rng(5)
     # 800 items → 50 concurrent waves; ~50 positives per user (the largest ≈ 80): 50 × 80 <
     # 1% of ~1M positives.  Skewed: user 0 holds all 800 items

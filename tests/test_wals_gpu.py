@@ -377,3 +377,61 @@ def test_whitening_grid_strides_bit_identical(k, monkeypatch):
         assert abs(l1 / (o.nusers * o.nitems) - lo) < 1e-9 * abs(lo), side
         c1.set_factors(side, o.factors(side))
         c2.set_factors(side, o.factors(side))
+
+
+def _destroy(c):
+    """qmfx_destroy with its return code checked (Context.close drops it)."""
+    assert qmf_amd.lib().qmfx_destroy(c.h) == 0
+    c.h = None
+
+
+def _lifecycle(precision):
+    """One create → use → destroy cycle over every subsystem that owns device buffers; every
+    call raises unless it returned 0.  Returns all the numbers it computed."""
+    k, nu, ni = 16, 40, 30
+    rng = np.random.default_rng(11)
+    base = np.arange(nu) * ni + np.arange(nu) % ni  # every user and every item once
+    rest = rng.permutation(np.setdiff1d(np.arange(nu * ni), base))[:260]
+    keys = rng.permutation(np.concatenate([base, rest]))  # 300 distinct (user, item) pairs
+    users, items = (keys // ni).astype(np.int64), (keys % ni).astype(np.int64)
+    values = rng.integers(1, 6, size=len(keys)).astype(np.float64)
+    uids, iids, ucsr, icsr = csr_from_triples(users, items, values)
+    assert len(uids) == nu and len(iids) == ni
+    out = []
+    c = qmf_amd.Context(k, precision)
+    c.set_shape(nu, ni)
+    c.upload_csr(0, *ucsr)
+    c.upload_csr(1, *icsr)
+    c.set_factors(1, rng.uniform(-0.01, 0.01, (ni, k)))
+    for side in (0, 1):
+        out.append(np.float64(c.wals_half(side, ALPHA, LAM)))
+        out.append(c.factors(side))
+    g = qmf_amd.Context(k, precision)
+    out.extend(g.group_signals(users, items, values))
+    for side in (0, 1):
+        out.extend(g.download_csr(side))
+    c.bpr_set_positives(users, items)
+    trip = np.stack([users[:8], items[:8], (items[:8] + 7) % ni], 1)
+    c.bpr_apply(trip, 0.05, 1.0, 0.025, 0.0025, True)
+    out += [c.factors(0), c.factors(1), c.bpr_biases()]
+    test_users = np.array([0, 7, 19, 39])
+    c.eval_set_labels(test_users, np.arange(5) * 2, np.tile([3, 11], 4), np.tile([1.0, 0.0], 4))
+    out.extend(c.eval_ranks(True))
+    _destroy(g)
+    _destroy(c)
+    return out
+
+
+@pytest.mark.parametrize("precision", [32, 64])
+def test_context_lifecycle_repeats_bit_equal(precision):
+    """The context owns its device buffers, events and streams and releases them in
+    qmfx_destroy.  Three create → WALS halves → device ingest (second context) → BPR update →
+    test-set ranks → destroy cycles in one process: what was released is reused, so every
+    cycle must succeed and compute the first cycle's factors and losses bit for bit."""
+    first = _lifecycle(precision)
+    assert all(np.all(np.isfinite(x)) for x in first)
+    for cycle in (2, 3):
+        again = _lifecycle(precision)
+        assert len(again) == len(first)
+        for n, (a, b) in enumerate(zip(first, again)):
+            assert np.array_equal(a, b), (cycle, n)
