@@ -301,23 +301,35 @@ inline bool use_big_rows(const qmfx_ctx* c) { return c->nt > 8; }
 // and ≤ 64, except on the streamed kernels' two-signals-per-lane buckets: fp32 k = 128 / 256
 // up to n = 128, fp64 k = 128 / 256 up to n = 80 (n = 81..96 spilled 64 VGPRs; those rows stay
 // direct).
-inline int max_whitened_ntn(const qmfx_ctx* c) {
-  if (!c->whitened_enabled) return 0;
-  if (c->nt == 4 && c->wb_k64_ntn > 0) return std::min(c->wb_k64_ntn, 4);
-  if (c->prec == 32) {
-    if (c->nt == 8 || c->nt == 16) return 8;
-    if (c->nt > 8) return 0;  // fp32 k = 144..240: every row on the big k×k kernel
+constexpr int default_whitened_ntn(int elem_bytes, int nt) {
+  if (elem_bytes == 4) {
+    if (nt == 8 || nt == 16) return 8;
+    if (nt > 8) return 0;  // fp32 k = 144..240: every row on the big k×k kernel
     // k = 64: n ≤ 64 (C2 same-box A/Bs, round 5: n ≤ 32 → n ≤ 48 10.0 → 9.1 ms/epoch, → n ≤ 64
     // 8.7 → 8.2)
-    if (c->nt == 4) return 4;
-    return std::min(c->nt / 2, 4);
+    if (nt == 4) return 4;
+    return nt / 2 < 4 ? nt / 2 : 4;
   }
-  if (c->nt == 8 || c->nt == 16) return 5;
-  if (c->nt > 8) return 0;
+  if (nt == 8 || nt == 16) return 5;
+  if (nt > 8) return 0;
   // k = 64: n ≤ 48 on the streamed fp64 kernel (C2 fp64 same-box A/B, round 5: 18.5 → 17.6
   // ms/epoch; n ≤ 64 measured no better)
-  if (c->nt == 4) return 3;
-  return std::min(c->nt / 2, c->nt <= 4 ? 2 : 4);
+  if (nt == 4) return 3;
+  return nt / 2 < 4 ? nt / 2 : 4;
+}
+// the policy never asks for a bucket without a kernel (wb_max_ntn, kernels.h)
+constexpr bool whitened_defaults_have_kernels() {
+  for (int nt = 1; nt <= 16; ++nt)
+    for (int eb = 4; eb <= 8; eb += 4)
+      if (default_whitened_ntn(eb, nt) > wb_max_ntn(eb, nt)) return false;
+  return true;
+}
+static_assert(whitened_defaults_have_kernels());
+inline int max_whitened_ntn(const qmfx_ctx* c) {
+  if (!c->whitened_enabled) return 0;
+  const int eb = c->prec == 32 ? 4 : 8;
+  const int want = c->nt == 4 && c->wb_k64_ntn > 0 ? c->wb_k64_ntn : default_whitened_ntn(eb, c->nt);
+  return std::min(want, wb_max_ntn(eb, c->nt));
 }
 
 inline int npieces(const qmfx_ctx* c) {

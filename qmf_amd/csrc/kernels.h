@@ -100,8 +100,17 @@ hipError_t launch_gram_big(const float* Y, int64_t n, int nt, float* G, double* 
                            int max_blocks, hipStream_t s);
 hipError_t launch_gram_big(const double* Y, int64_t n, int nt, double* G, double* partial,
                            int max_blocks, hipStream_t s);
-// whitened-row buckets: n ≤ 16·NTN, NTN = 1..kMaxNTN (NTN > 4 only for fp32 k = 256)
+// whitened-row buckets: n ≤ 16·NTN, NTN = 1..kMaxNTN
 constexpr int kMaxNTN = 8;
+// The largest bucket that has a whitened row kernel for factor tiling nt (KP = 16·nt), 0 for
+// none: n ≤ KP/2 and ≤ 64, except k = 64 (n ≤ 64) and the two-signals-per-lane buckets of
+// k = 128 / 256 (fp32 n ≤ 128, fp64 n ≤ 80).  launch_wals_woodbury builds exactly these.
+constexpr int wb_max_ntn(int elem_bytes, int nt) {
+  if (nt == 8 || nt == 16) return elem_bytes == 4 ? 8 : 5;
+  if (nt < 2 || nt > 8) return 0;
+  return nt == 4 ? 4 : nt / 2;
+}
+static_assert(wb_max_ntn(4, 16) <= kMaxNTN && wb_max_ntn(8, 16) <= kMaxNTN);
 hipError_t launch_wals_woodbury(const SolveArgs<float>& a, int nt, int ntn, hipStream_t s);
 hipError_t launch_wals_woodbury(const SolveArgs<double>& a, int nt, int ntn, hipStream_t s);
 // cus: compute units of the device (sizes the persistent grid)

@@ -6,6 +6,7 @@
 // solution by the push-through identity).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "chol.h"
 #include "common.h"
@@ -24,16 +25,10 @@ namespace qmfx {
 // and the HBM traffic per signal is one gathered row, as in the direct kernel.
 // Writes x' (whitened); whiten_kernel<UNWHITEN> maps it to x = L⁻ᵀ x' and adds −λ‖x‖².
 // ---------------------------------------------------------------------------------------
-// minimum waves per SIMD of the NTN = 4 tiling (timing experiments: 1 lifts the 256-VGPR cap)
-#ifndef QMFX_WB4_MIN_WAVES
-#define QMFX_WB4_MIN_WAVES 2
-#endif
-#ifndef QMFX_WB3_MIN_WAVES
-#define QMFX_WB3_MIN_WAVES 2
-#endif
-template <typename T, int NTK, int NTN, bool TRACE>
-__global__ __launch_bounds__(64, NTK > 8 ? 1 : (NTN == 4 ? QMFX_WB4_MIN_WAVES : (NTN == 3 ? QMFX_WB3_MIN_WAVES : 2)))
-void wals_woodbury_kernel(SolveArgs<T> a) {
+// fp64 k ≤ 48 only (NTN = 1): fp32 and fp64 k ≥ 64 run the streamed kernels below.
+template <int NTK, int NTN, bool TRACE>
+__global__ __launch_bounds__(64, 2) void wals_woodbury_kernel(SolveArgs<double> a) {
+  using T = double;
   using M = Mfma<T>;
   using acc_t = typename M::acc_t;
   using v4 = typename M::acc_t;  // 4-wide vector of T
@@ -1221,139 +1216,6 @@ __global__ __launch_bounds__(256) void chol_inv_kernel(const T* G, int k, double
   }
 }
 
-
-#ifndef QMFX_KERNELS_ONLY
-template <typename T, int NTK>
-static hipError_t launch_woodbury_ntk(const SolveArgs<T>& a, int ntn, hipStream_t s) {
-  if (a.nrows <= 0) return hipSuccess;
-  if (!a.desc) return hipErrorInvalidValue;
-  const dim3 b(64);
-  // fp32: the streamed kernel (every bucket); fp64 k ≤ 64: the register-resident one
-  if constexpr (sizeof(T) == 4) {
-    {
-#define QMFX_WBS(N)                                                                        \
-  return launch_row_chunks(a, 64, [&](const SolveArgs<T>& c) {                             \
-    hipLaunchKernelGGL((wals_woodbury_st_kernel<NTK, N>), dim3((unsigned)c.nrows), b, 0, s, c); \
-  })
-      switch (ntn) {
-        case 1: QMFX_WBS(1);
-        case 2:
-          if constexpr (NTK >= 4) QMFX_WBS(2);
-          return hipErrorInvalidValue;
-        case 3:
-          if constexpr (NTK >= 4) QMFX_WBS(3);
-          return hipErrorInvalidValue;
-        case 4:
-          if constexpr (NTK >= 4) QMFX_WBS(4);
-          return hipErrorInvalidValue;
-        // n = 65..128 (two signals per lane): fp32 k = 128 and 256
-        case 5:
-          if constexpr (NTK == 16 || NTK == 8) QMFX_WBS(5);
-          return hipErrorInvalidValue;
-        case 6:
-          if constexpr (NTK == 16 || NTK == 8) QMFX_WBS(6);
-          return hipErrorInvalidValue;
-        case 7:
-          if constexpr (NTK == 16 || NTK == 8) QMFX_WBS(7);
-          return hipErrorInvalidValue;
-        case 8:
-          if constexpr (NTK == 16 || NTK == 8) QMFX_WBS(8);
-          return hipErrorInvalidValue;
-        default: return hipErrorInvalidValue;
-      }
-#undef QMFX_WBS
-    }
-  } else {
-#define QMFX_WB(N)                                                                            \
-  return launch_row_chunks(a, 64, [&](const SolveArgs<T>& c) {                                \
-    if (c.trace)                                                                              \
-      hipLaunchKernelGGL((wals_woodbury_kernel<T, NTK, N, true>), dim3((unsigned)c.nrows), b, 0, s, c); \
-    else                                                                                      \
-      hipLaunchKernelGGL((wals_woodbury_kernel<T, NTK, N, false>), dim3((unsigned)c.nrows), b, 0, s, c); \
-  })
-  if (ntn == 1) {
-    QMFX_WB(1);
-  } else if (ntn == 2) {
-    if constexpr (NTK >= 4) QMFX_WB(2);
-    else return hipErrorInvalidValue;
-  } else if (ntn == 3) {
-    if constexpr (NTK >= 4) QMFX_WB(3);
-    else return hipErrorInvalidValue;
-  } else if (ntn == 4) {
-    if constexpr (NTK >= 8) QMFX_WB(4);
-    else return hipErrorInvalidValue;
-#undef QMFX_WB
-  } else {
-    return hipErrorInvalidValue;
-  }
-  }
-}
-
-template <int NTK>
-static hipError_t launch_woodbury_st64_ntk(const SolveArgs<double>& a, int ntn, hipStream_t s) {
-  if (a.nrows <= 0) return hipSuccess;
-  if (!a.desc) return hipErrorInvalidValue;
-#define QMFX_WBS64(N)                                                                      \
-  return launch_row_chunks(a, 64, [&](const SolveArgs<double>& c) {                        \
-    if (c.trace)                                                                           \
-      hipLaunchKernelGGL((wals_woodbury_st64_kernel<NTK, N, true>), dim3((unsigned)c.nrows), \
-                         dim3(64), 0, s, c);                                               \
-    else                                                                                   \
-      hipLaunchKernelGGL((wals_woodbury_st64_kernel<NTK, N>), dim3((unsigned)c.nrows),     \
-                         dim3(64), 0, s, c);                                               \
-  })
-  switch (ntn) {
-    case 1: QMFX_WBS64(1);
-    case 2: QMFX_WBS64(2);
-    case 3:
-      if constexpr (NTK >= 4) QMFX_WBS64(3);
-      return hipErrorInvalidValue;
-    case 4:
-      if constexpr (NTK >= 4) QMFX_WBS64(4);
-      return hipErrorInvalidValue;
-    // n = 65..80 (two signals per lane) at k = 128 and 256 (n > 80 spills: direct)
-    case 5:
-      if constexpr (NTK == 8 || NTK == 16) QMFX_WBS64(5);
-      return hipErrorInvalidValue;
-    default: return hipErrorInvalidValue;
-  }
-#undef QMFX_WBS64
-}
-
-template <typename T, int NT>
-static hipError_t launch_whiten_nt(const T* in, T* out, const int64_t* order, int64_t nrows,
-                                   const T* Linv, double* rowloss, double lambda, bool unwhiten,
-                                   int cus, hipStream_t s) {
-  if (nrows <= 0) return hipSuccess;
-  if constexpr (WhitenLds<T, NT>::FITS) {
-    if (cus <= 0) return hipErrorInvalidValue;
-    const int64_t need = (nrows + 8 * 16 * QMFX_WHITEN_LDS_RG - 1) / (8 * 16 * QMFX_WHITEN_LDS_RG);
-    int64_t cap = (int64_t)cus * WhitenLds<T, NT>::PER_CU;
-    // test hook (read per launch): fewer workgroups, so that every wave strides over several
-    // 32-row blocks at test sizes
-    if (const char* g = std::getenv("QMFX_WHITEN_GRID")) {
-      const long v = std::strtol(g, nullptr, 10);
-      if (v > 0 && v < cap) cap = v;
-    }
-    const unsigned grid = (unsigned)(need < cap ? need : cap);
-    if (unwhiten)
-      hipLaunchKernelGGL((whiten_lds_kernel<T, NT, true>), dim3(grid), dim3(512), 0, s, in, out,
-                         order, nrows, Linv, rowloss, lambda);
-    else
-      hipLaunchKernelGGL((whiten_lds_kernel<T, NT, false>), dim3(grid), dim3(512), 0, s, in,
-                         out, order, nrows, Linv, rowloss, lambda);
-    return hipGetLastError();
-  }
-  const unsigned blocks = (unsigned)((nrows + 64 * QMFX_WHITEN_RG - 1) / (64 * QMFX_WHITEN_RG));
-  if (unwhiten)
-    hipLaunchKernelGGL((whiten_kernel<T, NT, true>), dim3(blocks), dim3(256), 0, s, in, out, order,
-                       nrows, Linv, rowloss, lambda);
-  else
-    hipLaunchKernelGGL((whiten_kernel<T, NT, false>), dim3(blocks), dim3(256), 0, s, in, out,
-                       order, nrows, Linv, rowloss, lambda);
-  return hipGetLastError();
-}
-
 // The same factorization for KP > 128 (the fp64 matrix exceeds LDS): one 1024-thread
 // workgroup on a global fp64 scratch of KP·(KP+1) doubles (L2-resident; __syncthreads
 // orders the block's global accesses).  Once per half; ≈ms at KP = 256.
@@ -1419,6 +1281,90 @@ __global__ __launch_bounds__(1024) void chol_inv_global_kernel(const T* G, int k
   }
 }
 
+#ifndef QMFX_KERNELS_ONLY
+// f(integral_constant<int, ntn>) for 1 ≤ ntn ≤ MAX: the buckets wb_max_ntn gives a tiling are
+// the only ones instantiated
+template <int MAX, typename F>
+static hipError_t dispatch_ntn(int ntn, F&& f) {
+  if constexpr (MAX >= 1) {
+    if (ntn == MAX) return f(std::integral_constant<int, MAX>{});
+    return dispatch_ntn<MAX - 1>(ntn, f);
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
+
+// fp32: the streamed kernel at every tiling
+template <int NTK>
+static hipError_t launch_woodbury_f32_ntk(const SolveArgs<float>& a, int ntn, hipStream_t s) {
+  if (a.nrows <= 0) return hipSuccess;
+  if (!a.desc) return hipErrorInvalidValue;
+  return dispatch_ntn<wb_max_ntn(4, NTK)>(ntn, [&](auto N) {
+    return launch_row_chunks(a, 64, [&](const SolveArgs<float>& c) {
+      hipLaunchKernelGGL((wals_woodbury_st_kernel<NTK, decltype(N)::value>),
+                         dim3((unsigned)c.nrows), dim3(64), 0, s, c);
+    });
+  });
+}
+
+// fp64: k ≤ 48 on the register-resident kernel, k = 64 .. 128 and 256 on the streamed one
+template <int NTK>
+static hipError_t launch_woodbury_f64_ntk(const SolveArgs<double>& a, int ntn, hipStream_t s) {
+  if (a.nrows <= 0) return hipSuccess;
+  if (!a.desc) return hipErrorInvalidValue;
+  return dispatch_ntn<wb_max_ntn(8, NTK)>(ntn, [&](auto N) {
+    constexpr int NTN = decltype(N)::value;
+    return launch_row_chunks(a, 64, [&](const SolveArgs<double>& c) {
+      const dim3 grid((unsigned)c.nrows), b(64);
+      if constexpr (NTK < 4) {
+        if (c.trace)
+          hipLaunchKernelGGL((wals_woodbury_kernel<NTK, NTN, true>), grid, b, 0, s, c);
+        else
+          hipLaunchKernelGGL((wals_woodbury_kernel<NTK, NTN, false>), grid, b, 0, s, c);
+      } else {
+        if (c.trace)
+          hipLaunchKernelGGL((wals_woodbury_st64_kernel<NTK, NTN, true>), grid, b, 0, s, c);
+        else
+          hipLaunchKernelGGL((wals_woodbury_st64_kernel<NTK, NTN>), grid, b, 0, s, c);
+      }
+    });
+  });
+}
+
+template <typename T, int NT>
+static hipError_t launch_whiten_nt(const T* in, T* out, const int64_t* order, int64_t nrows,
+                                   const T* Linv, double* rowloss, double lambda, bool unwhiten,
+                                   int cus, hipStream_t s) {
+  if (nrows <= 0) return hipSuccess;
+  if constexpr (WhitenLds<T, NT>::FITS) {
+    if (cus <= 0) return hipErrorInvalidValue;
+    const int64_t need = (nrows + 8 * 16 * QMFX_WHITEN_LDS_RG - 1) / (8 * 16 * QMFX_WHITEN_LDS_RG);
+    int64_t cap = (int64_t)cus * WhitenLds<T, NT>::PER_CU;
+    // test hook (read per launch): fewer workgroups, so that every wave strides over several
+    // 32-row blocks at test sizes
+    if (const char* g = std::getenv("QMFX_WHITEN_GRID")) {
+      const long v = std::strtol(g, nullptr, 10);
+      if (v > 0 && v < cap) cap = v;
+    }
+    const unsigned grid = (unsigned)(need < cap ? need : cap);
+    if (unwhiten)
+      hipLaunchKernelGGL((whiten_lds_kernel<T, NT, true>), dim3(grid), dim3(512), 0, s, in, out,
+                         order, nrows, Linv, rowloss, lambda);
+    else
+      hipLaunchKernelGGL((whiten_lds_kernel<T, NT, false>), dim3(grid), dim3(512), 0, s, in,
+                         out, order, nrows, Linv, rowloss, lambda);
+  } else {
+    const unsigned blocks = (unsigned)((nrows + 64 * QMFX_WHITEN_RG - 1) / (64 * QMFX_WHITEN_RG));
+    if (unwhiten)
+      hipLaunchKernelGGL((whiten_kernel<T, NT, true>), dim3(blocks), dim3(256), 0, s, in, out,
+                         order, nrows, Linv, rowloss, lambda);
+    else
+      hipLaunchKernelGGL((whiten_kernel<T, NT, false>), dim3(blocks), dim3(256), 0, s, in, out,
+                         order, nrows, Linv, rowloss, lambda);
+  }
+  return hipGetLastError();
+}
+
 template <typename T, int NT>
 static hipError_t launch_chol_inv_nt(const T* G, int k, double lambda, T* Linv, int32_t* status,
                                      double* scratch, hipStream_t s) {
@@ -1436,23 +1382,13 @@ static hipError_t launch_chol_inv_nt(const T* G, int k, double lambda, T* Linv, 
 }
 
 hipError_t launch_wals_woodbury(const SolveArgs<float>& a, int nt, int ntn, hipStream_t s) {
-#define CALL(N) launch_woodbury_ntk<float, N>(a, ntn, s)
+#define CALL(N) launch_woodbury_f32_ntk<N>(a, ntn, s)
   QMFX_NT_SWITCH_W(nt, CALL)
 #undef CALL
 }
 hipError_t launch_wals_woodbury(const SolveArgs<double>& a, int nt, int ntn, hipStream_t s) {
-  // k = 64 .. 128 and 256 on the streamed fp64 kernel; the register-resident one below
-  switch (nt) {
-    case 4: return launch_woodbury_st64_ntk<4>(a, ntn, s);
-    case 5: return launch_woodbury_st64_ntk<5>(a, ntn, s);
-    case 6: return launch_woodbury_st64_ntk<6>(a, ntn, s);
-    case 7: return launch_woodbury_st64_ntk<7>(a, ntn, s);
-    case 8: return launch_woodbury_st64_ntk<8>(a, ntn, s);
-    case 16: return launch_woodbury_st64_ntk<16>(a, ntn, s);
-    default: break;
-  }
-#define CALL(N) launch_woodbury_ntk<double, N>(a, ntn, s)
-  QMFX_NT_SWITCH64(nt, CALL)
+#define CALL(N) launch_woodbury_f64_ntk<N>(a, ntn, s)
+  QMFX_NT_SWITCH_W(nt, CALL)
 #undef CALL
 }
 hipError_t launch_whiten(const float* in, float* out, const int64_t* order, int64_t nrows,

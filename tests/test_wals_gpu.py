@@ -208,6 +208,30 @@ def test_heavy_indefinite_rows_fallback(k):
         c.set_factors(side, o.factors(side))
 
 
+def test_indefinite_rows_on_whitened_route():
+    """Negative values on rows short enough to whiten (fp64 k = 32: the register-resident
+    whitened kernel): it flags them and writes x' = 0, and the pivoted re-solve gives the
+    oracle's factors, as on the direct routes of test_heavy_indefinite_rows_fallback."""
+    u, i, v = synth(2000, 300, 30000, seed=32)
+    v = v.copy()
+    v[::7] = -3.0
+    o, c = make_pair(u, i, v, 32, 64, seed=2)
+    assert c.row_classes(0)["whitened"][0] > 0
+    for side in (0, 1):
+        lo = o.iterate(side, NTHR)
+        ld = c.wals_half(side, ALPHA, LAM) / (o.nusers * o.nitems)
+        assert len(c.failed_rows()) > 0
+        assert rel_err(c.factors(side), o.factors(side)) < 1e-7, side
+        assert abs(ld - lo) < 1e-7 * abs(lo), side
+        c.set_factors(side, o.factors(side))
+
+
+# tilings whose whitened route no other case reaches → index of their largest bucket
+# (wb_max_ntn in kernels.h, minus one), which must hold rows
+TOP_BUCKET = {(48, 64, 30000): 0, (96, 64, 160000): 2, (48, 32, 30000): 0, (80, 32, 160000): 1,
+              (112, 32, 160000): 2}
+
+
 def test_row_system_matches_oracle():
     """qmfx_wals_row_system builds one row's k×k system on the device (A with λ, b, Σc)."""
     u, i, v = synth(500, 120, 8000, seed=3)
@@ -242,7 +266,7 @@ def test_row_system_matches_oracle():
     (128, 64, 400000),
     # fp64 k = 256 (C5 at the reference's precision): the streamed fp64 kernel beside the
     # big k×k kernel, every bucket up to n = 80
-    (256, 64, 30000), (256, 64, 160000), (256, 64, 400000)])
+    (256, 64, 30000), (256, 64, 160000), (256, 64, 400000)] + sorted(TOP_BUCKET))
 def test_whitened_rows_match_direct_and_oracle(k, precision, nnz, monkeypatch):
     """Short rows (n ≤ KP/2) take the whitened n×n path; the same half step with
     QMFX_NO_WHITEN=1 (direct k×k path for every row) and the oracle must agree."""
@@ -256,6 +280,9 @@ def test_whitened_rows_match_direct_and_oracle(k, precision, nnz, monkeypatch):
     if k == 64 and nnz == 160000:
         wb = c.row_classes(0)["whitened"]
         assert wb[2] > 0 and (wb[3] > 0) == (precision == 32), wb
+    if (k, precision, nnz) in TOP_BUCKET:
+        wb = c.row_classes(0)["whitened"]
+        assert wb[TOP_BUCKET[(k, precision, nnz)]] > 0, wb
     monkeypatch.setenv("QMFX_NO_WHITEN", "1")
     _, cd = make_pair(u, i, v, k, precision, seed=2)
     assert sum(cd.row_classes(0)["whitened"]) == 0

@@ -1,7 +1,7 @@
 #!/bin/bash
 # ISA of selected row kernels without building the whole library: direct.h's (or
 # SRC=woodbury.hip: woodbury.hip's) kernels with explicit instantiations only.  usage:
-# SRC=woodbury.hip tools/isa_one.sh out.s "template __global__ void qmfx::wals_woodbury_kernel<float, 8, 4, false>(qmfx::SolveArgs<float>);" [-Dflags]
+# SRC=woodbury.hip tools/isa_one.sh out.s "template __global__ void qmfx::wals_woodbury_kernel<3, 1, false>(qmfx::SolveArgs<double>);" [-Dflags]
 set -e
 OUT=$1; INST=$2; shift 2
 TU=$(mktemp /tmp/isa_one_XXXX.hip)
