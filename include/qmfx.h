@@ -135,7 +135,9 @@ int qmfx_bpr_epoch(qmfx_ctx* ctx, uint64_t seed, int num_neg, double lr, double 
 /* Applies the given (u, p, n) triplets in order with one wave (exact update order). */
 int qmfx_bpr_apply(qmfx_ctx* ctx, const int64_t* triplets, int64_t n, double lr,
                    double bias_lambda, double user_lambda, double item_lambda, int use_biases);
-/* Σ log(1+exp(−x̂)) over triplets (host array, uploaded and cached per `slot` 0/1). */
+/* Σ log(1+exp(−x̂)) over triplets (host array, uploaded and cached per `slot` 0/1).  The
+ * cache is keyed by the array's host address and length: another array or length is uploaded
+ * again, an array rewritten in place at the same length is not. */
 int qmfx_bpr_eval(qmfx_ctx* ctx, int slot, const int64_t* triplets, int64_t n, int use_biases,
                   double* loss_sum);
 

@@ -47,6 +47,9 @@ BprArgs<T> bpr_args(qmfx_ctx* c, double lr, double bl, double ul, double il, int
   // Above 1% (skewed user activity) its net change is added atomically like the item rows.
   a.atomic_user = (double)a.waves * (double)c->max_user_pos > 0.01 * (double)std::max<int64_t>(c->npos, 1) ? 1 : 0;
   if (const char* f = std::getenv("QMFX_BPR_ATOMIC_USER")) a.atomic_user = std::atoi(f) ? 1 : 0;
+  // 4097 rejections in a row have probability (positives/nitems)^4097 per draw: below 1e-35
+  // under 98% of the items, so only heavier users get the kernel that handles a capped draw
+  a.capped = (double)c->max_user_pos >= 0.98 * (double)c->s[1].n ? 1 : 0;
   return a;
 }
 

@@ -97,8 +97,8 @@ __device__ __forceinline__ bool bpr_step(const BprArgs<T>& a, int64_t u, int64_t
   const T eg = neg_sigmoid(x);
   if (!isfinite(eg)) return false;
   const T lr = a.lr;
-  // p == n (possible only in a caller-given sequence: sampled negatives are never positives):
-  // the reference updates q_n in place after q_p, so q_n's step starts from the new q_p
+  // p == n (a caller-given sequence, or a capped draw of a user who holds every item): the
+  // reference updates q_n in place after q_p, so q_n's step starts from the new q_p
   const bool same = p == n;
   if (a.use_biases && lane == 0) {
     const T bp_new = bp + lr * (eg - a.bias_lambda * bp);
@@ -275,7 +275,11 @@ __device__ __forceinline__ bool bpr_positive(const BprArgs<T>& a, int64_t u, int
 // iteration: (user, item) three positives ahead, the user's CSR range two ahead, its staged
 // positive list one ahead.  They are issued before the current positive's row loads, so
 // each iteration waits for about one memory latency instead of a chain of dependent loads.
-template <typename T, int E>
+// CAPPED (BprArgs::capped): a user holds nearly every item, so a draw can end at the attempt
+// cap with a positive, possibly p itself.  bpr_positive keeps q_p and q_n as two rows; such
+// a group takes the serial step instead (plain stores, q_n continued from the new q_p as the
+// reference does in place).  Every other dataset runs the kernel without that test.
+template <typename T, int E, bool CAPPED>
 __global__ __launch_bounds__(64) void bpr_epoch_kernel(BprArgs<T> a) {
   const int lane = threadIdx.x;
   const int64_t nw = (int64_t)gridDim.x;
@@ -317,6 +321,15 @@ __global__ __launch_bounds__(64) void bpr_epoch_kernel(BprArgs<T> a) {
       for (int j = 0; j < 4; ++j)
         if (j < nn)
           n[j] = draw_negative_t(a, a.uitems + rb0, cnt0, mine0, fk, 4099u * (uint32_t)(j0 + j), lane);
+      if (CAPPED) {
+        bool hits_p = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) hits_p |= j < nn && n[j] == p0;
+        if (hits_p) {
+          for (int j = 0; j < nn; ++j) ok &= bpr_step<T, E>(a, u0, p0, n[j], lane);
+          continue;
+        }
+      }
       ok &= bpr_positive<T, E>(a, u0, p0, n, nn, lane);
     }
     mine1 = lane < cnt1 ? mine1 : -1;
@@ -401,7 +414,10 @@ __global__ void sum_partials_kernel(const double* partial, int n, double* out) {
 
 template <typename T, int E>
 static hipError_t bpr_epoch(const BprArgs<T>& a, hipStream_t s) {
-  hipLaunchKernelGGL((bpr_epoch_kernel<T, E>), dim3(a.waves), dim3(64), 0, s, a);
+  if (a.capped)
+    hipLaunchKernelGGL((bpr_epoch_kernel<T, E, true>), dim3(a.waves), dim3(64), 0, s, a);
+  else
+    hipLaunchKernelGGL((bpr_epoch_kernel<T, E, false>), dim3(a.waves), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 template <typename T, int E>

@@ -186,6 +186,8 @@ struct BprArgs {
   int32_t* bad;            // set to 1 if a derivative was not finite
   int waves;               // concurrent waves of the epoch kernel (Hogwild width)
   int atomic_user;         // 1: add the user row's net change atomically (heavy users)
+  int capped;              // 1: some user holds ≥ 98% of the items, a draw can end at the
+                           // attempt cap with a positive (host-only: picks the kernel)
 };
 
 hipError_t launch_bpr_epoch(const BprArgs<float>& a, int kp, hipStream_t s);

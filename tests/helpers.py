@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (fixture loading, reference-format text)."""
+import functools
 import hashlib
 import os
 
@@ -65,3 +66,101 @@ def csr_from_triples(users, items, values):
         return np.cumsum(rp), cols[order].astype(np.int32), values[order]
 
     return uids, iids, side(uidx, iidx, len(uids)), side(iidx, uidx, len(iids))
+
+
+# ---- restatement of the BPR epoch's visiting order and negative draws (qmf_amd/csrc/bpr.hip
+# bpr_epoch_kernel, api_bpr.cpp qmfx_bpr_epoch): counter-based and keyed by positive slot, so
+# the multiset of (u, p, n) of an epoch does not depend on the number of waves
+M64 = (1 << 64) - 1
+M32 = (1 << 32) - 1
+
+
+def mix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
+    return x ^ (x >> 31)
+
+
+def fmix32(x):
+    x ^= x >> 16
+    x = (x * 0x85EBCA6B) & M32
+    x ^= x >> 13
+    x = (x * 0xC2B2AE35) & M32
+    return x ^ (x >> 16)
+
+
+def permutation(seed, npos, shuffle):
+    if not shuffle:
+        return 1, 0
+    pa = (mix64(seed ^ 0xA5A5A5A5) % npos) | 1
+    while np.gcd(pa, npos) != 1:
+        pa += 2
+    pa %= npos
+    pa = pa or 1
+    return pa, mix64(seed ^ 0x5A5A5A5A) % npos
+
+
+def triplets(users, items, nitems, seed, num_neg, shuffle):
+    npos = len(users)
+    pos = {}
+    for u, i in zip(users, items):
+        pos.setdefault(int(u), set()).add(int(i))
+    pa, pb = permutation(seed, npos, shuffle)
+    seed_key = mix64(seed ^ 0xB5AD4ECEDA1CE2A9)
+    out = []
+    for i in range(npos):
+        slot = (pa * i + pb) % npos
+        u, p = int(users[slot]), int(items[slot])
+        pkey = mix64(seed_key ^ slot)
+        fk = (pkey & M32) ^ (pkey >> 32)
+        for j in range(num_neg):
+            attempt = 0
+            while True:
+                h = fmix32((fk + ((4099 * j + attempt) * 0x9E3779B9)) & M32)
+                cand = (h * nitems) >> 32
+                if cand not in pos[u] or attempt >= 4096:
+                    break
+                attempt += 1
+            out.append((u, p, cand))
+    return np.array(out, np.int64)
+
+
+def bpr_wave_case(npos=4000):
+    """The multi-wave BPR epoch case shared by tests/test_bpr_kernels_gpu.py and its CPU
+    anchor in tests/test_oracle.py: 320 users × 320 items (20 concurrent waves on the
+    device), `npos` unique positives in random order."""
+    nu = ni = 320
+    rng = np.random.default_rng(320)
+    keys = rng.permutation(nu * ni)[:npos]
+    return nu, ni, (keys // ni).astype(np.int64), (keys % ni).astype(np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def bpr_wave_triplets(shuffle, npos=4000, num_neg=5):
+    """The (u, p, n) of the epoch with seed 31 (identity order) or 32 (shuffled) on
+    bpr_wave_case(npos).  Computed once per session; callers must not write to it."""
+    _, ni, users, items = bpr_wave_case(npos)
+    trip = triplets(users, items, ni, 32 if shuffle else 31, num_neg, shuffle)
+    trip.setflags(write=False)
+    return trip
+
+
+def bpr_linear_user(trip, I0, lr, nusers):
+    """U after the triplets from U0 = 0, to first order in lr (x̂ = O(lr), so the loss
+    derivative is ½ and the item rows move by O(lr²)): U[u] = ½·lr·Σ (I0[p] − I0[n])."""
+    U = np.zeros((nusers, I0.shape[1]))
+    np.add.at(U, trip[:, 0], 0.5 * lr * (I0[trip[:, 1]] - I0[trip[:, 2]]))
+    return U
+
+
+def bpr_linear_item(trip, U0, lr, nitems):
+    """(I, bias) after the triplets from I0 = 0, bias0 = 0, to first order in lr:
+    I[i] = ½·lr·(Σ_{p=i} U0[u] − Σ_{n=i} U0[u]), bias[i] = ½·lr·(#{p=i} − #{n=i})."""
+    I = np.zeros((nitems, U0.shape[1]))
+    b = np.zeros(nitems)
+    np.add.at(I, trip[:, 1], 0.5 * lr * U0[trip[:, 0]])
+    np.add.at(I, trip[:, 2], -0.5 * lr * U0[trip[:, 0]])
+    np.add.at(b, trip[:, 1], 0.5 * lr)
+    np.add.at(b, trip[:, 2], -0.5 * lr)
+    return I, b

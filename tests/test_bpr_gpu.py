@@ -14,61 +14,9 @@ import pytest
 
 import pyoracle as po
 import qmf_amd
+from helpers import fmix32, mix64, permutation, triplets  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-M64 = (1 << 64) - 1
-M32 = (1 << 32) - 1
-
-
-def mix64(x):
-    x = (x + 0x9E3779B97F4A7C15) & M64
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & M64
-    return x ^ (x >> 31)
-
-
-def fmix32(x):
-    x ^= x >> 16
-    x = (x * 0x85EBCA6B) & M32
-    x ^= x >> 13
-    x = (x * 0xC2B2AE35) & M32
-    return x ^ (x >> 16)
-
-
-def permutation(seed, npos, shuffle):
-    if not shuffle:
-        return 1, 0
-    pa = (mix64(seed ^ 0xA5A5A5A5) % npos) | 1
-    while np.gcd(pa, npos) != 1:
-        pa += 2
-    pa %= npos
-    pa = pa or 1
-    return pa, mix64(seed ^ 0x5A5A5A5A) % npos
-
-
-def triplets(users, items, nitems, seed, num_neg, shuffle):
-    npos = len(users)
-    pos = {}
-    for u, i in zip(users, items):
-        pos.setdefault(int(u), set()).add(int(i))
-    pa, pb = permutation(seed, npos, shuffle)
-    seed_key = mix64(seed ^ 0xB5AD4ECEDA1CE2A9)
-    out = []
-    for i in range(npos):
-        slot = (pa * i + pb) % npos
-        u, p = int(users[slot]), int(items[slot])
-        pkey = mix64(seed_key ^ slot)
-        fk = (pkey & M32) ^ (pkey >> 32)
-        for j in range(num_neg):
-            attempt = 0
-            while True:
-                h = fmix32((fk + ((4099 * j + attempt) * 0x9E3779B9)) & M32)
-                cand = (h * nitems) >> 32
-                if cand not in pos[u] or attempt >= 4096:
-                    break
-                attempt += 1
-            out.append((u, p, cand))
-    return np.array(out, np.int64)
 
 
 @pytest.mark.parametrize("precision,tol", [(64, 1e-12), (32, 1e-5)])

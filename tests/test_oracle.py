@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 
 import pyoracle as po
-from helpers import factor_text, load_ml100k, md5
+from helpers import (bpr_linear_item, bpr_linear_user, bpr_wave_case, bpr_wave_triplets,
+                     factor_text, load_ml100k, md5)
 
 MKL_DIR = "/opt/conda/lib"
 
@@ -156,6 +157,43 @@ def test_bpr_update_rule_matches_formula():
     np.testing.assert_allclose(I[4], I0[4] + lr * (-e * pu - li * I0[4]), rtol=1e-14)
     assert abs(bias[2] - (b0[2] + lr * (e - lb * b0[2]))) < 1e-14
     assert abs(bias[4] - (b0[4] + lr * (-e - lb * b0[4]))) < 1e-14
+
+
+def test_bpr_linearised_epoch_anchor():
+    """Anchors the fp64 tolerance (1e-6) of the linearised multi-wave tests in
+    test_bpr_kernels_gpu.py at their own shape (320 × 320, 4000 positives × 5 negatives,
+    k = 16, lr = 2⁻³⁰, λ = 0): BPREngine::update over the restated triplets, in data order and
+    in a random order, stays within 1e-7 of the first-order prediction, and one missing
+    triplet moves the result by more than 1e-3 (all relative to max|prediction|).
+    Measured: U 4.2e-09 / 3.9e-09, I 4.6e-09 / 5.1e-09, bias 1.8e-08 / 1.7e-08 (data /
+    random order); without the first triplet U moves by 4.6e-02, I by 3.6e-02, the biases by
+    1.8e-02."""
+    nu, ni, _, _ = bpr_wave_case()
+    trip = np.array(bpr_wave_triplets(False))
+    k, lr = 16, 2.0 ** -30
+    rng = np.random.default_rng(16)
+    I0 = rng.normal(0, 0.1, (ni, k))
+    U0 = rng.normal(0, 0.1, (nu, k))
+
+    def run(t):
+        U, I, b = np.zeros((nu, k)), I0.copy(), np.zeros(ni)
+        po.bpr_update_seq(U, I, b, t, lr, 0.0, 0.0, 0.0, True)
+        out = [U]
+        U, I, b = U0.copy(), np.zeros((ni, k)), np.zeros(ni)
+        po.bpr_update_seq(U, I, b, t, lr, 0.0, 0.0, 0.0, True)
+        return out + [I, b]
+
+    want = [bpr_linear_user(trip, I0, lr, nu), *bpr_linear_item(trip, U0, lr, ni)]
+    dist = lambda got, ref: [float(np.max(np.abs(g - r)) / np.abs(w).max())  # noqa: E731
+                             for g, r, w in zip(got, ref, want)]
+    serial = run(trip)
+    for name, t in (("serial", trip), ("random", trip[rng.permutation(len(trip))])):
+        err = dist(run(t), want)
+        print(name, "order: U %.2g I %.2g bias %.2g" % tuple(err))
+        assert max(err) < 1e-7, (name, err)
+    moved = dist(run(trip[1:]), serial)
+    print("one triplet dropped: U %.2g I %.2g bias %.2g" % tuple(moved))
+    assert min(moved) > 1e-3, moved
 
 
 def test_distribution_file_short_file(tmp_path):
