@@ -68,6 +68,81 @@ def csr_from_triples(users, items, values):
     return uids, iids, side(uidx, iidx, len(uids)), side(iidx, uidx, len(iids))
 
 
+# ---- the row-length ladder of tests/test_wals_rows_gpu.py (and its CPU anchor in
+# tests/test_oracle.py): one user row of every length at which a WALS row route changes
+LADDER_LENGTHS = tuple(range(171)) + (255, 256, 257, 383, 384, 385, 511, 512, 513, 640)
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_case(k, seed, precision, with_empty=True):
+    """((urp, ucol, uval), (irp, icol, ival), Y): one user row of every length in
+    LADDER_LENGTHS (181 rows, 18 631 signals; `with_empty=False` leaves the length-0 row out),
+    lengths assigned to rows by a seeded permutation, over max(1024, 4k) items; each row's
+    columns distinct and ascending; values uniform(0, 5) with every seventh exactly 0;
+    Y uniform(-0.01, 0.01).  precision 32 rounds the values and Y to fp32 first (then widens),
+    so a numpy fp64 reference solves exactly the problem an fp32 context holds.  Cached: the
+    arrays are read-only."""
+    rng = np.random.default_rng(seed)
+    nitems = max(1024, 4 * k)
+    lens = np.array([n for n in LADDER_LENGTHS if with_empty or n > 0], np.int64)
+    lens = rng.permutation(lens)
+    urp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    ucol = np.concatenate([np.sort(rng.choice(nitems, n, replace=False)) for n in lens])
+    ucol = ucol.astype(np.int32)
+    uval = rng.uniform(0.0, 5.0, int(urp[-1]))
+    uval[::7] = 0.0
+    Y = rng.uniform(-0.01, 0.01, (nitems, k))
+    if precision == 32:
+        uval = uval.astype(np.float32).astype(np.float64)
+        Y = Y.astype(np.float32).astype(np.float64)
+    rows = np.repeat(np.arange(len(lens)), lens)
+    order = np.lexsort((rows, ucol))  # by item, then user
+    irp = np.concatenate([[0], np.cumsum(np.bincount(ucol, minlength=nitems))]).astype(np.int64)
+    out = ((urp, ucol, uval), (irp, rows[order].astype(np.int32), uval[order]), Y)
+    for a in (*out[0], *out[1], Y):
+        a.setflags(write=False)
+    return out
+
+
+def ladder_reference(rowptr, col, val, Y, alpha, lam):
+    """Plain numpy fp64, row by row: A = YᵀY + Yᵣᵀ·diag(αv)·Yᵣ + λI, b = Yᵣᵀ(1 + αv),
+    x = solve(A, b), loss = Σc + xᵀ(A − λI)x − 2xᵀb (include/qmfx.h).  Returns
+    (X, loss, cond₂(A), S) per row, S = Σc + |xᵀ(A − λI)x| + 2|xᵀb| (the size of the loss's
+    terms: what a loss error is measured against)."""
+    Y = np.asarray(Y, np.float64)
+    k = Y.shape[1]
+    G = Y.T @ Y
+    nrows = len(rowptr) - 1
+    X = np.zeros((nrows, k))
+    loss, cond, S = np.zeros(nrows), np.zeros(nrows), np.zeros(nrows)
+    for r in range(nrows):
+        sl = slice(int(rowptr[r]), int(rowptr[r + 1]))
+        Yr = Y[col[sl]]
+        w = alpha * np.asarray(val[sl], np.float64)
+        M = G + (Yr.T * w) @ Yr  # A − λI
+        A = M + lam * np.eye(k)
+        b = Yr.T @ (1.0 + w)
+        x = np.linalg.solve(A, b)
+        quad, xb, cs = x @ M @ x, x @ b, float(np.sum(1.0 + w))
+        X[r] = x
+        loss[r] = cs + quad - 2.0 * xb
+        S[r] = cs + abs(quad) + 2.0 * abs(xb)
+        ev = np.linalg.eigvalsh(A)  # A is symmetric positive definite: cond₂ = λmax / λmin
+        cond[r] = ev[-1] / ev[0]
+    return X, loss, cond, S
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_solution(k, seed, precision, alpha, lam, with_empty=True):
+    """ladder_reference of ladder_case(k, seed, precision)'s user half, computed once per
+    session and shared by the cases on that problem; read-only."""
+    (urp, ucol, uval), _, Y = ladder_case(k, seed, precision, with_empty)
+    out = ladder_reference(urp, ucol, uval, Y, alpha, lam)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
 # ---- restatement of the BPR epoch's visiting order and negative draws (qmf_amd/csrc/bpr.hip
 # bpr_epoch_kernel, api_bpr.cpp qmfx_bpr_epoch): counter-based and keyed by positive slot, so
 # the multiset of (u, p, n) of an epoch does not depend on the number of waves

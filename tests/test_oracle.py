@@ -15,8 +15,9 @@ import numpy as np
 import pytest
 
 import pyoracle as po
-from helpers import (bpr_linear_item, bpr_linear_user, bpr_wave_case, bpr_wave_triplets,
-                     factor_text, load_ml100k, md5)
+from helpers import (LADDER_LENGTHS, bpr_linear_item, bpr_linear_user, bpr_wave_case,
+                     bpr_wave_triplets, factor_text, ladder_case, ladder_solution, load_ml100k,
+                     md5)
 
 MKL_DIR = "/opt/conda/lib"
 
@@ -194,6 +195,29 @@ def test_bpr_linearised_epoch_anchor():
     moved = dist(run(trip[1:]), serial)
     print("one triplet dropped: U %.2g I %.2g bias %.2g" % tuple(moved))
     assert min(moved) > 1e-3, moved
+
+
+@pytest.mark.parametrize("k", [17, 129])
+def test_ladder_reference_matches_oracle(k):
+    """Anchors the numpy reference of tests/test_wals_rows_gpu.py (helpers.ladder_reference)
+    on the CPU: on the row-length ladder without its empty row (the oracle builds rows from
+    signals), WALSEngine::iterate's restatement and the numpy row solves agree to 1e-11 per
+    row (‖Δx‖∞ / ‖x‖∞) and in the summed loss."""
+    lam, alpha = 0.05, 40.0
+    (urp, ucol, uval), (irp, icol, ival), Y = ladder_case(k, 1000 + k, 64, with_empty=False)
+    nu, ni = len(urp) - 1, len(irp) - 1
+    assert nu == len(LADDER_LENGTHS) - 1 and urp[-1] == sum(LADDER_LENGTHS) == 18631
+    assert sorted(np.diff(urp)) == sorted(LADDER_LENGTHS[1:])
+    o = po.OracleWALS.from_csr(nu, ni, urp, ucol, uval, irp, icol, ival, k, lam, alpha)
+    o.set_factors(1, Y)
+    lo = o.iterate(0) * nu * ni
+    X, loss, cond, S = ladder_solution(k, 1000 + k, 64, alpha, lam, with_empty=False)
+    err = np.max(np.abs(o.factors(0) - X), axis=1) / np.max(np.abs(X), axis=1)
+    print("k = %d: worst row %.2g, loss %.2g relative, largest cond %.3g"
+          % (k, err.max(), abs(lo - loss.sum()) / abs(loss.sum()), cond.max()))
+    assert err.max() < 1e-11, (int(np.argmax(err)), err.max())
+    assert abs(lo - loss.sum()) <= 1e-11 * abs(loss.sum())
+    assert np.all(S >= np.abs(loss))
 
 
 def test_distribution_file_short_file(tmp_path):
