@@ -290,12 +290,15 @@ inline int ensure_bias(qmfx_ctx* c) {
 }
 
 // YᵀY on the tiled multi-wave kernel (fp32 k > 128, fp64 k > 64)
-inline bool use_big(const qmfx_ctx* c) { return c->prec == 32 ? c->nt > 8 : c->nt > 4; }
+inline bool use_big(const qmfx_ctx* c) { return c->nt >= big_gram_min_nt(c->prec == 32 ? 4 : 8); }
+static_assert(big_gram_min_nt(4) == 8 + 1 && big_gram_min_nt(8) == 4 + 1,
+              "launch_gram builds the one-wave YᵀY up to nt = 8 (fp32) and 4 (fp64)");
 // direct rows on the multi-wave row kernel: k > 128 (fp64 k = 80..128 runs the one-wave
 // direct kernel with its accumulators across the VGPR + AGPR file; the
 // multi-wave kernel at fp64 k = 128 measured 213.7 ms per C3 item half at four waves per row
 // and 206.5 ms at two, against 179.2 / 175.6 ms here: round 6, profiles/r06/ab_big128_c3_f64.txt)
-inline bool use_big_rows(const qmfx_ctx* c) { return c->nt > 8; }
+inline bool use_big_rows(const qmfx_ctx* c) { return c->nt >= kBigRowMinNT; }
+static_assert(kBigRowMinNT == 8 + 1, "launch_wals_direct builds the one-wave rows up to nt = 8");
 
 // Largest whitened-row bucket (NTN: n ≤ 16·NTN) for this factor tiling: n ≤ KP/2
 // and ≤ 64, except on the streamed kernels' two-signals-per-lane buckets: fp32 k = 128 / 256

@@ -55,8 +55,8 @@ hipError_t launch_heavy_reduce(float* part, float* partb, double* partc, const i
 hipError_t launch_heavy_reduce(double* part, double* partb, double* partc, const int64_t* hseg,
                                int64_t h0, int64_t nh, const double* Gimg, int nt, hipStream_t s);
 
-// The same for the multi-wave k > 128 tilings (wals_big.hip): builds G + λI's tile image in
-// Gimg first (runtime tile count, no column permutation).
+// The same for the multi-wave k > 128 tilings (the rows of wals_big.hip; in wals_heavy.hip too):
+// builds G + λI's tile image in Gimg first (runtime tile count, no column permutation).
 hipError_t launch_heavy_reduce_big(float* part, float* partb, double* partc, const int64_t* hseg,
                                    int64_t h0, int64_t nh, const float* G, float* Gimg, int nt,
                                    int k, double lambda, hipStream_t s);
@@ -93,7 +93,14 @@ hipError_t launch_wals_direct(const SolveArgs<double>& a, int nt, hipStream_t s)
 // seg_mode 1 / 2 of the direct kernel (wals_heavy.hip; launch_wals_direct forwards there)
 hipError_t launch_wals_heavy(const SolveArgs<float>& a, int nt, hipStream_t s);
 hipError_t launch_wals_heavy(const SolveArgs<double>& a, int nt, hipStream_t s);
-// multi-wave row solve and tiled YᵀY for large factor counts (wals_big.hip; nt 5..16)
+// Multi-wave kernels for large factor counts, up to k = 256: the tilings each is built for
+// (ctx.h use_big_rows / use_big send exactly these there).  Row solve (wals_big.hip): k > 128.
+// Tiled YᵀY (gram_big.hip): fp32 k > 128, fp64 k > 64.
+constexpr int kBigMaxNT = 16;
+constexpr int kBigRowMinNT = 9;
+constexpr int big_gram_min_nt(int elem_bytes) { return elem_bytes == 4 ? 9 : 5; }
+static_assert(big_gram_min_nt(4) <= kBigRowMinNT && big_gram_min_nt(8) <= kBigRowMinNT,
+              "a side on the multi-wave row kernel takes its YᵀY from the tiled kernel");
 hipError_t launch_wals_big(const SolveArgs<float>& a, int nt, hipStream_t s);
 hipError_t launch_wals_big(const SolveArgs<double>& a, int nt, hipStream_t s);
 hipError_t launch_gram_big(const float* Y, int64_t n, int nt, float* G, double* partial,

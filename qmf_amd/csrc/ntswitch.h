@@ -1,5 +1,20 @@
 // Host-side dispatch of a runtime tile count to the kernel template instances.
 #pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+// f(integral_constant<int, nt>) for LO ≤ nt ≤ HI, hipErrorInvalidValue otherwise: only the
+// tilings of the range are instantiated (the multi-wave kernels' ranges are in kernels.h)
+template <int LO, int HI, typename F>
+hipError_t dispatch_nt(int nt, F&& f) {
+  if constexpr (LO <= HI) {
+    if (nt == LO) return f(std::integral_constant<int, LO>{});
+    return dispatch_nt<LO + 1, HI>(nt, f);
+  } else {
+    return hipErrorInvalidValue;
+  }
+}
 
 #define QMFX_NT_SWITCH(NTV, CALL)         \
   switch (NTV) {                          \

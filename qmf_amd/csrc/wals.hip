@@ -25,8 +25,9 @@
 // This file: YᵀY, the G + λI tile image of the direct kernel, the fixed-order loss sum and
 // the MFMA layout self-test.  The direct row kernel is csrc/direct.h (instantiated by
 // wals_direct_f32.hip / wals_direct_f64.hip / wals_heavy.hip), the whitened kernels
-// woodbury.hip, the multi-wave k > 128 kernels wals_big.hip.
+// woodbury.hip, the multi-wave k > 128 row kernel wals_big.hip, its tiled YᵀY gram_big.hip.
 #include "direct.h"
+#include "gram_reduce.h"
 
 namespace qmfx {
 
@@ -96,24 +97,7 @@ __global__ __launch_bounds__(64) void gram_partial_kernel(const T* Y, int64_t n,
   }
 }
 
-// Fixed-order sum of the partials: 16 outputs per 256-thread block, each summed as 16
-// consecutive chunks of blocks (thread (chunk, output)), then the chunk sums in order —
-// deterministic, and 16× the parallelism of one thread per output (C2: 0.32 → ~0.03 ms).
-__device__ __forceinline__ double gram_reduce_one(const double* partial, int nblocks,
-                                                  int64_t stride, int off, double (*red)[16],
-                                                  int o, int ch) {
-  const int cs = (nblocks + 15) / 16;
-  const int b0 = ch * cs, b1 = b0 + cs < nblocks ? b0 + cs : nblocks;
-  double s = 0.0;
-  for (int b = b0; b < b1; ++b) s += partial[(int64_t)b * stride + off];
-  red[ch][o] = s;
-  __syncthreads();
-  double t = 0.0;
-  if (ch == 0)
-    for (int c = 0; c < 16; ++c) t += red[c][o];
-  return t;
-}
-
+// the partials summed in fixed order (gram_reduce.h), mirrored into the upper triangle
 template <typename T, int NT>
 __global__ __launch_bounds__(256) void gram_reduce_kernel(const double* partial, int nblocks, T* G) {
   constexpr int KP = 16 * NT;

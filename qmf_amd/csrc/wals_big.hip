@@ -1,120 +1,31 @@
-// WALS row solve for large factor counts (fp32 k > 128, fp64 k > 64; up to k = 256).
+// WALS row solve for large factor counts (k > 128, up to k = 256; NT = 9..16).
 //
 // Reference path: WALSEngine::updateFactorsForOne (qmf/wals/WALSEngine.cpp:266-310) and
 // linearSymmetricSolve → dsysv_ (qmf/Matrix.cpp:81-96), as in wals.hip.  At large k one
 // wave cannot hold the k×k system in registers, so one WORKGROUP of NW waves solves a row:
+// the NT(NT+1)/2 lower 16×16 tiles of A are spread over the waves (big_tile, big.h) and stay
+// in their registers for the whole solve.  A row runs in one of three configurations (BigCfg):
 //
-//   * the NT(NT+1)/2 lower 16×16 tiles of A are distributed round-robin over the waves and
-//     stay in their registers for the whole solve;
-//   * Gram: the row's fixed-side rows are staged into LDS SIG signals at a time (double
-//     buffer, register-staged loads of the next stage in flight during the MFMAs); every
-//     wave reads its tiles' operands from LDS, so the tile→wave map is a runtime table;
-//   * Cholesky, right-looking over 16-column panels: owners write panel column p to LDS,
-//     wave 0 factors its diagonal block and the next 48 rows, the waves solve the remaining
-//     rows 64 at a time in parallel (with the forward solve of b), then every wave applies
-//     the rank-16 trailing update to its own tiles with MFMA (operands from the LDS panel);
-//   * backward solve by 16-blocks: owners of L(J, I) tiles add their part of Lᵀx in LDS,
-//     wave 0 finishes the block with the diagonal triangle.
+//   | rows            | Gram                        | tile map                    | solve    |
+//   | fp64            | streamed (big_gram_stream)  | pair at NT = 16, else       | LDLᵀ     |
+//   |                 |                             | round-robin; compile time   |          |
+//   | fp32, NT = 16   | split-bf16 (big_split_mfma) | pair; compile time          | LDLᵀ     |
+//   | fp32, NT 9..15  | LDS-staged (big_gram_step)  | round-robin; run time       | Cholesky |
+//
+//   * staged Gram: the row's fixed-side rows are staged into LDS SIG signals at a time (double
+//     buffer, register-staged loads of the next stage in flight during the MFMAs);
+//   * LDLᵀ: big_ldl_solve, one wave-specialised copy of the whole row solve per wave;
+//   * Cholesky, right-looking over 16-column panels: owners write panel column p to LDS, every
+//     wave factors the diagonal block and its own rows below it (big_panel_all, with the
+//     forward solve of b), then applies the rank-16 trailing update to its own tiles with
+//     MFMA (big_trailing); backward solve by 16-blocks: owners of L(J, I) tiles add their
+//     part of Lᵀx in LDS, wave 0 finishes the block with the diagonal triangle.
 // Same results contract as the single-wave kernels: status[row] = 1 on a non-positive pivot.
-#include <type_traits>
-#include <utility>
-
-#include "common.h"
-
-// `#pragma unroll 2` on the Gram step loops is not honoured for every tiling (those keep a
-// rolled loop); dropping the hint costs the fp32 NT = 16 kernels 24-44 VGPRs, so it stays
-#pragma clang diagnostic ignored "-Wpass-failed"
-#include "kernels.h"
-#include "rowsolve.h"
+#include "big.h"
 #include "chol.h"
-
-#ifndef QMFX_BIG_SIG32
-#define QMFX_BIG_SIG32 32
-#endif
-#ifndef QMFX_BIG_NW32
-#define QMFX_BIG_NW32 8  // waves per row at fp32 k > 160
-#endif
-#ifndef QMFX_BIG_SIG64
-#define QMFX_BIG_SIG64 16
-#endif
-#ifndef QMFX_BIG_SPLIT
-#define QMFX_BIG_SPLIT 1  // fp32 k = 256: the split-bf16 Gram from LDS (QMFX_BIG_SPLIT=0: f32 MFMA)
-#endif
-#ifndef QMFX_BIG_STREAM
-#define QMFX_BIG_STREAM 1  // fp64: per-wave streamed Gram (0: the LDS-staged Gram)
-#endif
-#ifndef QMFX_BIG_LDL32
-#define QMFX_BIG_LDL32 1  // fp32 k = 256: wave-specialised rows with the LDLᵀ (0: the Cholesky)
-#endif
-#ifndef QMFX_BIG_PAIR64
-#define QMFX_BIG_PAIR64 1  // fp64 k = 256: row-pair tile map (0: round-robin)
-#endif
+#include "ntswitch.h"
 
 namespace qmfx {
-
-template <typename T, int NT>
-struct BigCfg {
-  static constexpr int KP = 16 * NT;
-  static constexpr int NTT = NT * (NT + 1) / 2;
-  // waves per row: ≤ 17 fp32 / ≤ 10 fp64 accumulator tiles per wave (fp64 NT ≤ 8: the tiled
-  // YᵀY only; those rows run the one-wave direct kernel)
-  static constexpr int NW = sizeof(T) == 4 ? (NT <= 10 ? 4 : QMFX_BIG_NW32) : (NT <= 8 ? 4 : 8);
-  // split-bf16 Gram (fp32, NT = 2·NW): the loader threads split each staged element once
-  // into bf16 hi/mid/lo planes ([column][signal], 32 signals = one 16x16x32 MFMA K step)
-  // and wave W owns block rows W and NT−1−W (NT + 1 tiles), reading each column block's
-  // planes once per stage for both rows
-  static constexpr bool SPLIT = sizeof(T) == 4 && NT == 2 * NW && QMFX_BIG_SPLIT;
-  // fp64: every wave gathers its own operand fragments of the row's signals (big_gram_stream),
-  // with no LDS staging and no barrier in the Gram
-  static constexpr bool STREAM = sizeof(T) == 8 && QMFX_BIG_STREAM;
-  // row-pair tile map (wave W owns block rows W and NT−1−W: NT + 1 tiles)
-  static constexpr bool PAIR = SPLIT || (STREAM && NT == 2 * NW && QMFX_BIG_PAIR64);
-  // one wave-specialised copy of the row solve per wave (compile-time tile map) and the LDLᵀ
-  // factorization (big_ldl_solve): the streamed fp64 rows and the split fp32 rows
-  static constexpr bool WSPEC = STREAM || (SPLIT && QMFX_BIG_LDL32);
-  // waves per SIMD the row kernel is compiled for (512-thread workgroups: two)
-  static constexpr int WPE = (64 * NW + 255) / 256;
-  // LDLᵀ panel buffers: two (no barrier between a panel's readers and the next panel's
-  // stores), or one when more than two workgroups share a CU's LDS
-  static constexpr bool PANEL2 = WSPEC && (NT > 8 || WPE <= 2);
-  static constexpr int TPW = PAIR ? NT + 1 : (NTT + NW - 1) / NW;
-  static constexpr int SPAD = 40;  // bf16 per plane column (32 signals + 16 B pad: no bank conflicts)
-  static constexpr int NTHR = 64 * NW;
-  static constexpr int SIG = sizeof(T) == 4 ? QMFX_BIG_SIG32 : QMFX_BIG_SIG64;  // signals per LDS stage
-  static constexpr int VEC = 16 / sizeof(T);             // elements per 16-B load
-  static constexpr int CPR = KP / VEC;                   // 16-B chunks per row
-  static constexpr int TRIPS = (SIG * CPR + NTHR - 1) / NTHR;
-  // padded LDS row of a panel (fp32: 16-B aligned rows for the b128 row accesses)
-  static constexpr int PLD = sizeof(T) == 4 ? 20 : 17;
-  // compile-time tile map with LDS fragments reused across a wave's tiles (Gram and
-  // trailing update); the fp64 tilings above NT = 11 lack the registers for it
-  static constexpr bool REUSE = sizeof(T) == 4 || NT <= 11;
-};
-
-// tile s of wave W: round-robin t = W + NW·s, or (split map) rows W and NT−1−W
-template <typename C>
-__host__ __device__ constexpr void big_tile(int W, int s, int& I, int& J) {
-  if constexpr (C::PAIR) {
-    constexpr int NT = C::KP / 16;
-    if (s <= W) {
-      I = W;
-      J = s;
-    } else {
-      I = NT - 1 - W;
-      J = s - W - 1;
-    }
-  } else {
-    const int t = W + C::NW * s;
-    if (t < C::NTT) {
-      int i = 0;
-      while ((i + 1) * (i + 2) / 2 <= t) ++i;
-      I = i;
-      J = t - i * (i + 1) / 2;
-    } else {
-      I = J = -1;
-    }
-  }
-}
 
 template <typename T, int NT>
 struct BigShared {
@@ -123,16 +34,16 @@ struct BigShared {
   union {
     T stage[2][C::STREAM ? 1 : C::SIG * C::KP];
     uint16_t planes[2][3][C::SPLIT ? C::KP * C::SPAD : 1];  // split Gram: bf16 hi/mid/lo, [column][signal]
-    float bred[8][C::KP];                    // split Gram: per-wave b partials (after the Gram)
+    float bred[C::NQ][C::KP];                // split Gram: per-quad b partials (after the Gram)
     struct {
       T panel[C::KP * C::PLD];
       T Ldiag[NT * 16 * C::PLD];
-      T panel2[C::PANEL2 ? C::KP * C::PLD : 1];  // LDLᵀ factorization: odd panels
+      T panel2[C::WSPEC ? C::KP * C::PLD : 1];  // LDLᵀ factorization: odd panels
     };
   };
   T w[2][C::SIG];   // α·v of the staged signals (0 past the row end)
   T c[2][C::SIG];   // 1 + α·v (0 past the row end)
-  double cred[8];   // split Gram: per-wave Σc
+  double cred[C::NQ];  // split Gram: per-quad Σc (streamed Gram: Σc in slot 0)
   int negw;         // split Gram: some signal has a negative weight (row goes to the re-solve)
   T bw[C::KP];
   T borig[C::KP];
@@ -144,17 +55,6 @@ struct BigShared {
   int bad;  // wave 0's pivot flag, for every wave's output stores
 };
 
-// Calls f(integral_constant<W>) for the wave-uniform wave index wv (compile-time tile maps).
-template <int NW, int W = 0, typename F>
-__device__ __forceinline__ void dispatch_wave(int wv, F&& f) {
-  if constexpr (W < NW) {
-    if (wv == W)
-      f(std::integral_constant<int, W>{});
-    else
-      dispatch_wave<NW, W + 1>(wv, f);
-  }
-}
-
 // Panel p on every wave at once: lanes 0..15 of each wave hold the diagonal block (factored
 // redundantly, as in the head), lanes 16..63 rows 48W + 16 .. 48W + 63 of the panel; each
 // wave runs the head's column loop on its own rows, so the serial head and the slot phase
@@ -164,6 +64,8 @@ __device__ void big_panel_all(BigShared<T, NT>& S, int p, int wv, int lane, int&
   constexpr int KP = 16 * NT;
   constexpr int PLD = BigCfg<T, NT>::PLD;
   const int R = KP - 16 * p;
+  static_assert(std::is_same_v<T, float> && !BigCfg<T, NT>::WSPEC,
+                "the readlane Cholesky serves the fp32 rows below k = 256 only");
   static_assert(48 * BigCfg<T, NT>::NW + 16 >= KP, "panel rows beyond the waves' lanes");
   if (wv > 0 && 48 * wv + 16 >= R) return;  // no rows below the diagonal block for this wave
   const int q = lane < 16 ? lane : 48 * wv + lane;
@@ -210,27 +112,6 @@ __device__ void big_panel_all(BigShared<T, NT>& S, int p, int wv, int lane, int&
     S.yd[16 * p + lane] = yv;
 #pragma unroll
     for (int c = 0; c < 16; ++c) S.Ldiag[(p * 16 + lane) * PLD + c] = c <= lane ? pa[c] : T(0);
-  }
-}
-
-// One 4-signal step of the Gram for the tiles of wave W (t = W + NW·s, compile-time map):
-// the wave reads each 16-row fragment of the staged signals once (NT LDS reads instead of
-// two per tile) and reuses it for every tile in its tile row or column.
-template <typename T, int NT, int W>
-__device__ __forceinline__ void big_gram_step(typename Mfma<T>::acc_t* acc, const T* yk, T wk) {
-  using C = BigCfg<T, NT>;
-  using M = Mfma<T>;
-  T y[NT], wy[NT];
-#pragma unroll
-  for (int J = 0; J < NT; ++J) {
-    y[J] = yk[16 * J];
-    wy[J] = wk * y[J];
-  }
-#pragma unroll
-  for (int s = 0; s < C::TPW; ++s) {
-    int I = -1, J = -1;
-    big_tile<C>(W, s, I, J);
-    if (I >= 0) acc[s] = M::mma(y[I], wy[J], acc[s]);
   }
 }
 
@@ -516,6 +397,7 @@ __device__ __forceinline__ void big_ldl_solve(BigShared<T, NT>& S,
                                               int lane, int& bad, uint64_t* sub = nullptr) {
   using C = BigCfg<T, NT>;
   using M = Mfma<T>;
+  static_assert(C::WSPEC, "the LDLᵀ needs the compile-time tile map");
   constexpr int KP = C::KP, TPW = C::TPW, PLD = C::PLD;
   const int cl = lane & 15, kk = lane >> 4;
   // (QMFX_BIG_SUBTRACE diagnostics builds: cycles of (a), (b), (c) and the backward solve)
@@ -523,7 +405,7 @@ __device__ __forceinline__ void big_ldl_solve(BigShared<T, NT>& S,
   auto stamp = [&]() -> uint64_t { return sub ? __builtin_amdgcn_s_memtime() : 0; };
   t0 = stamp();
   for (int p = 0; p < NT; ++p) {
-    T* P = (C::PANEL2 && (p & 1)) ? S.panel2 : S.panel;
+    T* P = (p & 1) ? S.panel2 : S.panel;
     const int R = KP - 16 * p;
     // (a)
 #pragma unroll
@@ -621,8 +503,6 @@ __device__ __forceinline__ void big_ldl_solve(BigShared<T, NT>& S,
         }
       }
     }
-    // one panel buffer: its readers finish before the next panel's stores
-    if constexpr (!C::PANEL2) __syncthreads();
     if (sub) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const uint64_t t = stamp();
@@ -677,9 +557,9 @@ __device__ __forceinline__ void big_ldl_solve(BigShared<T, NT>& S,
 // solve (slot = heavy row of a.desc: the reduced image of the row's first segment in place of
 // G + λI and the Gram).  The reference loops a heavy row inside one thread
 // (WALSEngine.cpp:277-287); SURVEY.md §5 "long rows".
-// WV ≥ 0: the body of wave WV alone, with its tile map at compile time (the streamed fp64
-// Gram: one wave-specialised copy of the whole row solve per wave, so no accumulator values
-// merge across the waves' code paths); WV = −1: one body for every wave (runtime tile map).
+// C::WSPEC: the body of wave WV alone, with its tile map at compile time (one wave-specialised
+// copy of the whole row solve per wave, so no accumulator values merge across the waves' code
+// paths); otherwise WV = −1: one body for every wave (runtime tile map).
 template <typename T, int NT, int MODE, int WV>
 __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T, NT>& S) {
   using C = BigCfg<T, NT>;
@@ -690,7 +570,8 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
   constexpr int CPR = C::CPR, TRIPS = C::TRIPS, PLD = C::PLD;
 
   const int tid = threadIdx.x;
-  const int wv = WV >= 0 ? WV : __builtin_amdgcn_readfirstlane(tid >> 6);
+  static_assert((WV >= 0) == C::WSPEC, "a wave index at compile time exactly on the wave-specialised rows");
+  const int wv = C::WSPEC ? WV : __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lane = tid & 63;
   const int cl = lane & 15;
   const int kk = lane >> 4;
@@ -750,9 +631,10 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
   int negw = 0;       // split Gram: a negative weight (the split needs √w)
   if constexpr (C::SPLIT) {
     // loader thread: column group g (columns 4g..4g+3), signals 4q..4q+3 of each stage
-    // (KP/4 groups × 8 quads = 32·NT = the workgroup's threads when NT = 2·NW)
+    // (KP/4 groups × NQ quads = 32·NT = the workgroup's threads when NT = 2·NW)
     constexpr int NG4 = KP / 4;
-    static_assert(NG4 * 8 == C::NTHR, "split loader: one (column group, quad) per thread");
+    static_assert(NG4 * C::NQ == C::NTHR && 4 * C::NQ == SIG,
+                  "split loader: one (column group, quad) per thread");
     const int g = tid % NG4, q = tid / NG4;
     int colq[4];
     float valq[4];
@@ -823,7 +705,7 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
         __syncthreads();
       }
     }
-    // b and Σc: per-wave partials in fixed order
+    // b and Σc: per-quad partials in fixed order
 #pragma unroll
     for (int m = 0; m < 4; ++m) S.bred[q][4 * g + m] = bpart[m];
     if (g == 0) S.cred[q] = csl;
@@ -831,11 +713,11 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
     if (tid < KP) {
       float b = 0.f;
 #pragma unroll
-      for (int w = 0; w < 8; ++w) b += S.bred[w][tid];
+      for (int w = 0; w < C::NQ; ++w) b += S.bred[w][tid];
       bp = b;
     }
     if (tid == 0)
-      for (int w = 0; w < 8; ++w) cs += S.cred[w];
+      for (int w = 0; w < C::NQ; ++w) cs += S.cred[w];
     __syncthreads();
   } else if constexpr (C::STREAM) {
     const int n = (int)(end - beg);
@@ -867,6 +749,8 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
     if (tid < KP) bp = S.bw[tid];
     if (tid == 0) cs = S.cred[0];
   } else {
+  static_assert(std::is_same_v<T, float> && C::REUSE,
+                "the LDS-staged Gram serves the fp32 rows below k = 256 only");
   int cols[TRIPS];
   vec_t stg[TRIPS];
   T wmeta = T(0), cmeta = T(0);
@@ -930,19 +814,7 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
           big_gram_step<T, NT, W>(acc, sg + (k4 + kk) * KP + cl, S.w[buf][k4 + kk]);
       };
       static_assert(NW == 2 || NW == 4 || NW == 8 || NW == 16, "wave count");
-      if constexpr (C::REUSE) {
-        dispatch_wave<NW>(wv, gram_stage);
-      } else {
-#pragma unroll 2
-        for (int k4 = 0; k4 < SIG; k4 += 4) {
-          const T* yk = sg + (k4 + kk) * KP + cl;
-          const T wk = S.w[buf][k4 + kk];
-#pragma unroll
-          for (int s = 0; s < TPW; ++s) {
-            if (TI[s] >= 0) acc[s] = M::mma(yk[16 * TI[s]], wk * yk[16 * TJ[s]], acc[s]);
-          }
-        }
-      }
+      dispatch_wave<NW>(wv, gram_stage);
       if (tid < KP) {
 #pragma unroll 4
         for (int k = 0; k < SIG; ++k) bp += S.c[buf][k] * sg[k * KP + tid];
@@ -995,7 +867,7 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
 #ifdef QMFX_BIG_SUBTRACE
   uint64_t sub[4] = {0, 0, 0, 0};
 #endif
-  if constexpr (C::WSPEC && WV >= 0) {
+  if constexpr (C::WSPEC) {
 #ifdef QMFX_BIG_SUBTRACE
     big_ldl_solve<T, NT, WV>(S, acc, lane, bad, trace ? sub : nullptr);
 #else
@@ -1025,17 +897,7 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
           acc[s][r] = S.panel[(16 * (TI[s] - p) + M::crow(lane, r)) * PLD + cl];
       }
     }
-    if constexpr (!C::REUSE) {
-#pragma unroll
-      for (int s = 0; s < TPW; ++s) {
-        if (TJ[s] > p) {
-          const T* li = S.panel + (16 * (TI[s] - p) + cl) * PLD + kk;
-          const T* lj = S.panel + (16 * (TJ[s] - p) + cl) * PLD + kk;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc[s] = M::mma(-li[4 * q], lj[4 * q], acc[s]);
-        }
-      }
-    } else if (p + 1 < NT) {
+    if (p + 1 < NT) {
       auto trailing = [&](auto wtag) {
         big_trailing<T, NT, decltype(wtag)::value>(acc, S.panel, p, cl, kk);
       };
@@ -1114,7 +976,7 @@ __device__ __forceinline__ void big_row_body(const SolveArgs<T>& a, BigShared<T,
       for (int j = 0; j < 5; ++j) o[j] = tr[j];
       o[5] = hw | ((uint64_t)xcc << 32);
 #ifdef QMFX_BIG_SUBTRACE
-      if constexpr (C::WSPEC && WV >= 0) {
+      if constexpr (C::WSPEC) {
         // diagnostics record: start, (a), (b), (c), backward, Gram cycles, n, row
         o[1] = sub[0];
         o[2] = sub[1];
@@ -1141,114 +1003,7 @@ __global__ __launch_bounds__((BigCfg<T, NT>::NTHR), (BigCfg<T, NT>::WPE)) void w
   }
 }
 
-// ---- YᵀY for large NT, every tile per workgroup: the block's rows are staged through LDS
-// SIG at a time with coalesced 16-B loads, so Y is read from HBM once (a strip per block
-// row read it NT times: 42 -> 4 ms per launch at C5), and the waves split the NT(NT+1)/2
-// tiles as in the row kernel's Gram (big_gram_step, weight 1).
-template <typename T, int NT>
-__global__ __launch_bounds__((BigCfg<T, NT>::NTHR)) void gram_tiles_kernel(
-    const T* Y, int64_t n, int64_t rows_per_block, double* partial) {
-  using C = BigCfg<T, NT>;
-  using M = Mfma<T>;
-  using acc_t = typename M::acc_t;
-  using vec_t = T __attribute__((ext_vector_type(C::VEC)));
-  constexpr int KP = C::KP, NW = C::NW, TPW = C::TPW, NTT = C::NTT, SIG = C::SIG;
-  constexpr int CPR = C::CPR, TRIPS = C::TRIPS;
-  __shared__ __attribute__((aligned(16))) T stage[SIG * KP];
-
-  const int tid = threadIdx.x;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lane = tid & 63;
-  const int cl = lane & 15;
-  const int kk = lane >> 4;
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = r0 + rows_per_block < n ? r0 + rows_per_block : n;
-
-  int TI[TPW], TJ[TPW];
-  acc_t acc[TPW];
-#pragma unroll
-  for (int s = 0; s < TPW; ++s) {
-    big_tile<C>(wv, s, TI[s], TJ[s]);
-    acc[s] = acc_t{0, 0, 0, 0};
-  }
-
-  // the next stage's rows are loaded into registers while this stage's MFMAs run (the
-  // same rows in the same order: the partials are bit-identical to a load-then-compute loop)
-  vec_t nx[TRIPS];
-  auto fetch = [&](int64_t e0) {
-#pragma unroll
-    for (int t = 0; t < TRIPS; ++t) {
-      const int ch = tid + C::NTHR * t;
-      const int64_t e = e0 + ch / CPR;
-      nx[t] = (ch < SIG * CPR && e < r1)
-                  ? *(reinterpret_cast<const vec_t*>(Y + e * KP) + ch % CPR)
-                  : vec_t{};
-    }
-  };
-  if (r0 < r1) fetch(r0);
-  for (int64_t e0 = r0; e0 < r1; e0 += SIG) {
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < TRIPS; ++t) {
-      const int ch = tid + C::NTHR * t;
-      if (ch < SIG * CPR) reinterpret_cast<vec_t*>(stage)[ch] = nx[t];
-    }
-    __syncthreads();
-    if (e0 + SIG < r1) fetch(e0 + SIG);
-    if constexpr (C::REUSE) {
-      auto step = [&](auto wtag) {
-#pragma unroll 2
-        for (int k4 = 0; k4 < SIG; k4 += 4)
-          big_gram_step<T, NT, decltype(wtag)::value>(acc, stage + (k4 + kk) * KP + cl, T(1));
-      };
-      dispatch_wave<NW>(wv, step);
-    } else {
-      for (int k4 = 0; k4 < SIG; k4 += 4) {
-        const T* yk = stage + (k4 + kk) * KP + cl;
-#pragma unroll
-        for (int s = 0; s < TPW; ++s)
-          if (TI[s] >= 0) acc[s] = M::mma(yk[16 * TI[s]], yk[16 * TJ[s]], acc[s]);
-      }
-    }
-  }
-  double* out = partial + (int64_t)blockIdx.x * NTT * 256;
-#pragma unroll
-  for (int s = 0; s < TPW; ++s) {
-    if (TI[s] >= 0) {
-      const int t = tile_index(TI[s], TJ[s]);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) out[t * 256 + M::crow(lane, r) * 16 + cl] = (double)acc[s][r];
-    }
-  }
-}
-
-// fixed-order fp64 sum of the per-block partials + mirror (runtime NT): 16 outputs per
-// block, 16 chunk sums each, then the chunks in order (as gram_reduce_kernel in wals.hip)
-template <typename T>
-__global__ __launch_bounds__(256) void gram_reduce_rt_kernel(const double* partial, int nblocks,
-                                                             int nt, T* G) {
-  __shared__ double red[16][16];
-  const int KP = 16 * nt;
-  const int NTT = nt * (nt + 1) / 2;
-  const int o = threadIdx.x & 15, ch = threadIdx.x >> 4;
-  const int idx = blockIdx.x * 16 + o;
-  const int i = idx / KP, j = idx % KP;
-  const int ii = i >= j ? i : j, jj = i >= j ? j : i;
-  const int t = tile_index(ii >> 4, jj >> 4);
-  const int off = t * 256 + (ii & 15) * 16 + (jj & 15);
-  const int cs = (nblocks + 15) / 16;
-  const int b0 = ch * cs, b1 = b0 + cs < nblocks ? b0 + cs : nblocks;
-  double sum = 0.0;
-  for (int b = b0; b < b1; ++b) sum += partial[(int64_t)b * NTT * 256 + off];
-  red[ch][o] = sum;
-  __syncthreads();
-  if (ch == 0) {
-    double tot = 0.0;
-    for (int c = 0; c < 16; ++c) tot += red[c][o];
-    G[idx] = (T)tot;
-  }
-}
-
+#ifndef QMFX_KERNELS_ONLY
 template <typename T, int NT, int MODE>
 static hipError_t launch_big_mode(const SolveArgs<T>& a, hipStream_t s) {
   return launch_row_chunks(a, BigCfg<T, NT>::NTHR, [&](const SolveArgs<T>& c) {
@@ -1256,172 +1011,22 @@ static hipError_t launch_big_mode(const SolveArgs<T>& a, hipStream_t s) {
                        dim3(BigCfg<T, NT>::NTHR), 0, s, c);
   });
 }
-template <typename T, int NT>
-static hipError_t launch_big_nt(const SolveArgs<T>& a, hipStream_t s) {
-  if (a.nrows <= 0) return hipSuccess;
-  if (a.seg_mode == 1) return launch_big_mode<T, NT, 1>(a, s);
-  if (a.seg_mode == 2) return launch_big_mode<T, NT, 2>(a, s);
-  return launch_big_mode<T, NT, 0>(a, s);
-}
-
-template <typename T, int NT>
-static hipError_t launch_gram_tiles_nt(const T* Y, int64_t n, double* partial, int nblocks,
-                                       int64_t rows_per_block, hipStream_t s) {
-  if (nblocks > 0)
-    hipLaunchKernelGGL((gram_tiles_kernel<T, NT>), dim3(nblocks), dim3(BigCfg<T, NT>::NTHR), 0,
-                       s, Y, n, rows_per_block, partial);
-  return hipGetLastError();
-}
-
-// G + λI (padding diagonal 1) as the big kernel's tile image [tile][lane][4] (no column
-// permutation: the big kernel's tiles are canonical), for the split-K reduction
 template <typename T>
-__global__ void gimg_big_kernel(const T* G, int nt, int k, double lambda, T* img) {
-  using M = Mfma<T>;
-  const int KP = 16 * nt, NTT = nt * (nt + 1) / 2;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= NTT * 256) return;
-  const int r = idx & 3, lane = (idx >> 2) & 63, t = idx >> 8;
-  int I = 0;
-  while (tile_index(I + 1, 0) <= t) ++I;
-  const int J = t - tile_index(I, 0);
-  const int i = 16 * I + M::crow(lane, r), j = 16 * J + (lane & 15);
-  double g = (double)G[(int64_t)i * KP + j];
-  if (i == j) g += (i < k) ? lambda : 1.0;
-  img[idx] = (T)g;
+static hipError_t wals_big(const SolveArgs<T>& a, int nt, hipStream_t s) {
+  return dispatch_nt<kBigRowMinNT, kBigMaxNT>(nt, [&](auto N) {
+    constexpr int NT = decltype(N)::value;
+    if (a.nrows <= 0) return hipSuccess;
+    if (a.seg_mode == 1) return launch_big_mode<T, NT, 1>(a, s);
+    if (a.seg_mode == 2) return launch_big_mode<T, NT, 2>(a, s);
+    return launch_big_mode<T, NT, 0>(a, s);
+  });
 }
-
-// Split-K second pass for the big tilings (runtime tile count; heavy_reduce_kernel's contract,
-// wals_heavy.hip): one workgroup of 256 threads per (heavy row, tile) sums the row's segments
-// in segment order in fp64 with G + λI, rounds once and writes over the first segment's
-// slot; tile index NTT takes the rhs, Σc and the flag.
-template <typename T>
-__global__ __launch_bounds__(256) void heavy_reduce_big_kernel(T* part, T* partb, double* partc,
-                                                               const int64_t* hseg, int64_t h0,
-                                                               const T* Gimg, int nt) {
-  const int KP = 16 * nt, NTT = nt * (nt + 1) / 2;
-  const int t = blockIdx.y;
-  const int64_t h = h0 + blockIdx.x;
-  const int64_t s0 = hseg[h], s1 = hseg[h + 1];
-  const int tid = threadIdx.x;
-  if (t < NTT) {
-    const int64_t off = (int64_t)t * 256 + tid;
-    double v = (double)Gimg[off];
-    for (int64_t s = s0; s < s1; ++s) v += (double)part[s * ((int64_t)NTT * 256) + off];
-    part[s0 * ((int64_t)NTT * 256) + off] = (T)v;
-  } else {
-    for (int j = tid; j < KP; j += 256) {
-      double b = 0.0;
-      for (int64_t s = s0; s < s1; ++s) b += (double)partb[s * KP + j];
-      partb[s0 * KP + j] = (T)b;
-    }
-    if (tid == 0) {
-      double c = 0.0, f = 0.0;
-      for (int64_t s = s0; s < s1; ++s) {
-        c += partc[2 * s];
-        f = fmax(f, partc[2 * s + 1]);
-      }
-      partc[2 * s0] = c;
-      partc[2 * s0 + 1] = f;
-    }
-  }
-}
-
-template <typename T>
-static hipError_t heavy_reduce_big(T* part, T* partb, double* partc, const int64_t* hseg,
-                                   int64_t h0, int64_t nh, const T* G, T* Gimg, int nt, int k,
-                                   double lambda, hipStream_t s) {
-  const int NTT = nt * (nt + 1) / 2;
-  hipLaunchKernelGGL((gimg_big_kernel<T>), dim3(NTT), dim3(256), 0, s, G, nt, k, lambda, Gimg);
-  for (int64_t done = 0; done < nh; done += 65535) {
-    const int64_t cnt = nh - done < 65535 ? nh - done : 65535;
-    hipLaunchKernelGGL((heavy_reduce_big_kernel<T>), dim3((unsigned)cnt, NTT + 1), dim3(256), 0,
-                       s, part, partb, partc, hseg, h0 + done, (const T*)Gimg, nt);
-  }
-  return hipGetLastError();
-}
-hipError_t launch_heavy_reduce_big(float* part, float* partb, double* partc, const int64_t* hseg,
-                                   int64_t h0, int64_t nh, const float* G, float* Gimg, int nt,
-                                   int k, double lambda, hipStream_t s) {
-  return heavy_reduce_big(part, partb, partc, hseg, h0, nh, G, Gimg, nt, k, lambda, s);
-}
-hipError_t launch_heavy_reduce_big(double* part, double* partb, double* partc, const int64_t* hseg,
-                                   int64_t h0, int64_t nh, const double* G, double* Gimg, int nt,
-                                   int k, double lambda, hipStream_t s) {
-  return heavy_reduce_big(part, partb, partc, hseg, h0, nh, G, Gimg, nt, k, lambda, s);
-}
-
-#define QMFX_BIG_SWITCH(NTV, CALL)        \
-  switch (NTV) {                          \
-    case 5: return CALL(5);               \
-    case 6: return CALL(6);               \
-    case 7: return CALL(7);               \
-    case 8: return CALL(8);               \
-    case 9: return CALL(9);               \
-    case 10: return CALL(10);             \
-    case 11: return CALL(11);             \
-    case 12: return CALL(12);             \
-    case 13: return CALL(13);             \
-    case 14: return CALL(14);             \
-    case 15: return CALL(15);             \
-    case 16: return CALL(16);             \
-    default: return hipErrorInvalidValue; \
-  }
-
-#ifdef QMFX_BIG_DEV16
-// (register / ISA inspection builds only: the k = 256 instances alone)
-#undef QMFX_BIG_SWITCH
-#define QMFX_BIG_SWITCH(NTV, CALL) return NTV == 16 ? CALL(16) : hipErrorInvalidValue;
-#define QMFX_BIG_ROW_SWITCH(NTV, CALL) return NTV == 16 ? CALL(16) : hipErrorInvalidValue;
-#else
-// the row kernel takes k > 128 only (ctx.h use_big_rows); the tiled YᵀY also fp64 k = 80..128
-#define QMFX_BIG_ROW_SWITCH(NTV, CALL)    \
-  switch (NTV) {                          \
-    case 9: return CALL(9);               \
-    case 10: return CALL(10);             \
-    case 11: return CALL(11);             \
-    case 12: return CALL(12);             \
-    case 13: return CALL(13);             \
-    case 14: return CALL(14);             \
-    case 15: return CALL(15);             \
-    case 16: return CALL(16);             \
-    default: return hipErrorInvalidValue; \
-  }
-#endif
 hipError_t launch_wals_big(const SolveArgs<float>& a, int nt, hipStream_t s) {
-#define CALL(N) launch_big_nt<float, N>(a, s)
-  QMFX_BIG_ROW_SWITCH(nt, CALL)
-#undef CALL
+  return wals_big(a, nt, s);
 }
 hipError_t launch_wals_big(const SolveArgs<double>& a, int nt, hipStream_t s) {
-#define CALL(N) launch_big_nt<double, N>(a, s)
-  QMFX_BIG_ROW_SWITCH(nt, CALL)
-#undef CALL
+  return wals_big(a, nt, s);
 }
-template <typename T>
-static hipError_t gram_big(const T* Y, int64_t n, int nt, T* G, double* partial, int max_blocks,
-                           hipStream_t s) {
-  int64_t rpb = (n + max_blocks - 1) / max_blocks;
-  rpb = ((rpb + 3) / 4) * 4;
-  if (rpb < 64) rpb = 64;
-  const int nblocks = (int)((n + rpb - 1) / rpb);
-  hipError_t e = hipSuccess;
-#define CALL(N) launch_gram_tiles_nt<T, N>(Y, n, partial, nblocks, rpb, s)
-  e = [&]() -> hipError_t { QMFX_BIG_SWITCH(nt, CALL) }();
-#undef CALL
-  if (e != hipSuccess) return e;
-  const int KP = 16 * nt;
-  hipLaunchKernelGGL((gram_reduce_rt_kernel<T>), dim3(KP * KP / 16), dim3(256), 0, s,
-                     partial, nblocks, nt, G);
-  return hipGetLastError();
-}
-hipError_t launch_gram_big(const float* Y, int64_t n, int nt, float* G, double* partial,
-                           int max_blocks, hipStream_t s) {
-  return gram_big(Y, n, nt, G, partial, max_blocks, s);
-}
-hipError_t launch_gram_big(const double* Y, int64_t n, int nt, double* G, double* partial,
-                           int max_blocks, hipStream_t s) {
-  return gram_big(Y, n, nt, G, partial, max_blocks, s);
-}
+#endif  // QMFX_KERNELS_ONLY
 
 }  // namespace qmfx

@@ -1,7 +1,9 @@
 #!/bin/bash
-# ISA of selected row kernels without building the whole library: direct.h's (or
-# SRC=woodbury.hip: woodbury.hip's) kernels with explicit instantiations only.  usage:
+# ISA of selected row kernels without building the whole library: direct.h's (or SRC=<unit>:
+# woodbury.hip's, wals_big.hip's, gram_big.hip's, wals_heavy.hip's) kernels with explicit
+# instantiations only.  usage:
 # SRC=woodbury.hip tools/isa_one.sh out.s "template __global__ void qmfx::wals_woodbury_kernel<3, 1, false>(qmfx::SolveArgs<double>);" [-Dflags]
+# SRC=wals_big.hip tools/isa_one.sh out.s "template __global__ void qmfx::wals_big_kernel<double, 16, 0>(qmfx::SolveArgs<double>);"
 set -e
 OUT=$1; INST=$2; shift 2
 TU=$(mktemp /tmp/isa_one_XXXX.hip)
