@@ -158,6 +158,36 @@ int qmfx_eval_set_labels(qmfx_ctx* ctx, int64_t ntest, const int64_t* users,
 int qmfx_eval_ranks(qmfx_ctx* ctx, int use_biases, double* label_scores, int64_t* above,
                     double* sq_sum);
 
+/* ---- top-N recommendations -------------------------------------------------------------------
+ * For each of the nusers requested users (user idx; any order, repeats allowed) the device
+ * scores every item and selects the user's best eligible items, without the dense score
+ * matrix.  score(u, i) is exactly qmfx_eval_ranks' score: the item bias when use_biases (else
+ * 0.0), then s = s + u_f * q_f for f = 0..k-1 in double, one rounded multiply and one rounded
+ * add each, on the factor values the device holds (an fp32 context's values widened).
+ * Item a ranks before item b when score_a > score_b, or score_a == score_b and a < b: the
+ * comparison is numeric (-0.0 equals +0.0, then the index decides).  NaN scores are out of
+ * contract: the order is undefined then.
+ * Eligible items, by `exclude`: every item (QMFX_REC_ALL), or every item not in the user's
+ * seen list: the user's row of the side-0 CSR (QMFX_REC_UNSEEN_SIGNALS; needs the column
+ * indices ascending within a row, which qmfx_group_signals and the synthetic generators
+ * guarantee and which is the caller's precondition for qmfx_upload_csr), or the user's
+ * qmfx_bpr_set_positives items (QMFX_REC_UNSEEN_POSITIVES).
+ * User t's recommendation is the first counts[t] = min(topn, eligible) eligible items in that
+ * order: items[t*topn + r] (item idx) and scores[t*topn + r] for rank r; the unused tail
+ * carries item -1 and score 0.0.  topn is 1..QMFX_REC_MAX_N.
+ * Fails (-1, with a message) on: topn out of range, a user index out of range, an exclude
+ * mode whose data is absent, use_biases without biases, nfactors > 256, no factors.  On a
+ * context sharded by qmfx_dist_init* QMFX_REC_UNSEEN_SIGNALS accepts only users of this
+ * rank's row range (it holds no other rows' signals); the other two modes work on any rank,
+ * the factors being full replicas.  nusers == 0 succeeds and touches nothing. */
+#define QMFX_REC_MAX_N 128
+#define QMFX_REC_ALL 0              /* every item is eligible */
+#define QMFX_REC_UNSEEN_SIGNALS 1   /* minus the user's row of the side-0 CSR (WALS) */
+#define QMFX_REC_UNSEEN_POSITIVES 2 /* minus the user's qmfx_bpr_set_positives list (BPR) */
+int qmfx_recommend(qmfx_ctx* ctx, int64_t nusers, const int64_t* users, int topn, int exclude,
+                   int use_biases, int64_t* items /*nusers·topn*/, double* scores /*nusers·topn*/,
+                   int32_t* counts /*nusers*/);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) -------------------------------------- */
 int qmfx_rccl_unique_id(uint8_t* id128);
 /* Joins the RCCL communicator (id128 from rank 0's qmfx_rccl_unique_id), takes this rank's
@@ -187,7 +217,8 @@ int qmfx_dist_plan(const int64_t* rowptr, int64_t nrows, int world, int npieces,
                    int64_t* pbounds);
 
 /* ---- measurement -------------------------------------------------------------------------- */
-/* HIP-event time of the row-solve kernel launches (on the context stream) since reset. */
+/* HIP-event time of the row-solve kernel launches (on the context stream) since reset; the
+ * kernels of qmfx_bpr_epoch and qmfx_recommend calls are counted here too. */
 int qmfx_solve_kernel_stats(qmfx_ctx* ctx, double* total_ms, int64_t* launches,
                             double* flops, double* bytes);
 /* Per kernel class since reset: 0 = direct row kernel, 1 = whitened row kernels (row solve

@@ -56,6 +56,7 @@ SIGNATURES = {
     "qmfx_bpr_eval": [vp, c_int, P_i64, c_i64, c_int, P_f64],
     "qmfx_eval_set_labels": [vp, c_i64, P_i64, P_i64, P_i64, P_f64],
     "qmfx_eval_ranks": [vp, c_int, P_f64, P_i64, P_f64],
+    "qmfx_recommend": [vp, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64, P_i32],
     "qmfx_rccl_unique_id": [P_u8],
     "qmfx_dist_init": [vp, c_int, c_int, P_u8],
     "qmfx_partition_rows": [P_i64, c_i64, c_int, c_int, P_i64, P_i64],
@@ -371,6 +372,21 @@ class Context:
         _check(lib().qmfx_eval_ranks(self.h, int(use_biases), _p(ls, P_f64), _p(ab, P_i64),
                                      _p(sq, P_f64)))
         return ls, ab, sq
+
+    # ---- top-N recommendations
+    def recommend(self, users, topn, exclude=0, use_biases=False):
+        """(items[n, topn], scores[n, topn], counts[n]) for the user indices `users`: see
+        include/qmfx.h qmfx_recommend (exclude: 0 all items, 1 minus the side-0 CSR row,
+        2 minus the BPR positives)."""
+        users = np.ascontiguousarray(users, np.int64)
+        n, w = len(users), max(int(topn), 0)
+        items = np.empty((n, w), np.int64)
+        scores = np.empty((n, w), np.float64)
+        counts = np.empty(n, np.int32)
+        _check(lib().qmfx_recommend(self.h, n, _p(users, P_i64), int(topn), int(exclude),
+                                    int(use_biases), _p(items, P_i64), _p(scores, P_f64),
+                                    _p(counts, P_i32)))
+        return items, scores, counts
 
     # ---- dist / stats
     def dist_init(self, rank, world, uid):

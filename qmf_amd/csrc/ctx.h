@@ -162,6 +162,12 @@ struct qmfx_ctx {
   qmfx::DevPtr<double> ev_lscore, ev_pscore;
   qmfx::DevPtr<unsigned long long> ev_above;
   qmfx::DevPtr<double> ev_sq, ev_udbl;
+  // top-N recommendations (qmfx_recommend): scratch grown on demand (rc_cap: bytes held, in
+  // the members' order)
+  qmfx::DevPtr<int64_t> rc_users, rc_items;
+  qmfx::DevPtr<double> rc_udbl, rc_pscore, rc_scores;
+  qmfx::DevPtr<int32_t> rc_pitem, rc_pcnt, rc_counts;
+  size_t rc_cap[8] = {};
   uint64_t bpr_epochs = 0;
   // QMFX_FAULT_COMM_RANK=<rank>[:<after>] (tests), read once at create: that rank's piece
   // broadcasts fail as if RCCL had failed once <after> of them have succeeded (-1: none)

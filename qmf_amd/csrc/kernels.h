@@ -276,4 +276,34 @@ int64_t eval_batch_groups();
 hipError_t launch_eval_ranks(const EvalArgs<float>& a, hipStream_t s);
 hipError_t launch_eval_ranks(const EvalArgs<double>& a, hipStream_t s);
 
+// Top-N recommendations (recommend.hip)
+constexpr int kRecMaxN = 128;  // QMFX_REC_MAX_N
+template <typename T>
+struct RecArgs {
+  const T* U;                // [nu][kp]
+  const T* I;                // [ni][kp]
+  const T* bias;             // [ni] item biases or nullptr
+  const int64_t* users;      // [nreq] requested user rows (any order, repeats allowed)
+  int64_t nreq;
+  int64_t nitems;
+  int k, kp;
+  int topn;                  // 1..kRecMaxN
+  // the users' seen items, ascending within a user: row r is seen_col[seen_ptr[r]] ..
+  // seen_col[seen_ptr[r + 1]]; seen_ptr = nullptr: every item is eligible
+  const int64_t* seen_ptr;
+  const int32_t* seen_col;
+  double* udbl;              // [eval_user_rows(nreq)][k] scratch: one batch's users' rows
+  // per-chunk survivors of one batch, [eval_chunks(nreq, nitems)][eval_user_rows(nreq)] lists
+  double* part_score;        // [lists][topn]
+  int32_t* part_item;        // [lists][topn]
+  int32_t* part_cnt;         // [lists]
+  int64_t* items;            // [nreq][topn] out: item rows in rank order, −1 in the unused tail
+  double* scores;            // [nreq][topn] out: their scores, 0.0 in the unused tail
+  int32_t* counts;           // [nreq] out: min(topn, eligible items)
+  int64_t chunk;             // set by the launcher
+  int64_t t_base, nbatch;    // set by the launcher: first user and user rows of the batch
+};
+hipError_t launch_recommend(const RecArgs<float>& a, hipStream_t s);
+hipError_t launch_recommend(const RecArgs<double>& a, hipStream_t s);
+
 }  // namespace qmfx

@@ -1,0 +1,413 @@
+// Top-N recommendations on the device (qmfx_recommend): for each requested user, the first
+// min(N, eligible) eligible items in the order "higher score first, equal scores by ascending
+// item index", without the dense n_users × n_items score matrix.
+//
+//   rec_users_kernel   the requested users' factor rows as doubles, [groups·32][k] in the
+//                      [t/8][f][t%8] layout of eval_users_kernel (zero padded);
+//   rec_select_kernel  grid (item chunks, groups of 32 users), 4 waves of 8 users: scores a
+//                      64-item tile exactly as eval_rank_kernel does (the tile staged through
+//                      LDS in 64-column stages, the users' rows wave-uniform through the scalar
+//                      cache), then, per user, appends the items that are valid, unseen and
+//                      rank before the user's threshold to that user's LDS candidate list
+//                      (ballot + prefix count; a list belongs to one wave, so no atomics).
+//                      A list that could not take another full tile is pruned by its wave to
+//                      the best N in rank order (rank counting in LDS), which also raises the
+//                      threshold (the N-th best so far).  Per chunk the ≤ N survivors go to a
+//                      global partial buffer [chunk][user][N];
+//   rec_merge_kernel   one wave per user: streams the user's chunks × N partial candidates
+//                      through the same append / prune steps and writes items (int64), scores
+//                      and the count, the unused tail as item −1 / score 0.0.
+//
+// Scores are eval.hip's: bias (or 0), then one rounded multiply and one rounded add per factor
+// in factor order, no fused multiply-add, so they equal the host's double scores bit for bit
+// and every user's list is uniquely defined (the chunks hold disjoint items and the order
+// compares the global item index, so ties break the same way across chunks).  NaN scores are
+// out of contract: the order is not total then (no access leaves a list whatever the scores).
+// "Seen" items: the user's ascending list (side-0 CSR row or sorted BPR positives).  A cursor
+// per user walks the list with the tiles; the entries inside the tile's item range (the
+// window, wave-uniform bounds) are held one per lane and each lane binary-searches them for
+// its item with lane shuffles.  Bound: fp64 VALU (2 instructions per multiply-add).
+//
+// LDS of rec_select_kernel (dynamic, one configuration): 32 lists × 256 × 12 B = 96 KiB, the
+// per-user state 1,280 B, the item tile 64 × 66 × sizeof(T): 133,376 B (fp64) / 116,480 B
+// (fp32), one workgroup per CU.
+#include "common.h"
+#include "kernels.h"
+
+namespace qmfx {
+namespace {
+
+constexpr int RC_TI = 64;               // items per tile (one per lane)
+constexpr int RC_UW = 8;                // users per wave
+constexpr int RC_W = 4;                 // waves per workgroup
+constexpr int RC_UG = RC_UW * RC_W;     // users per workgroup
+constexpr int RC_KC = 64;               // factor columns per LDS stage
+constexpr int RC_KMAX = 256;
+constexpr int RC_TS = RC_KC + 2;        // tile row stride (even: 8-byte aligned pairs)
+constexpr int RC_CAP = 256;             // candidates per list (≥ kRecMaxN + RC_TI)
+static_assert(RC_CAP >= kRecMaxN + RC_TI, "a pruned list must take another full tile");
+
+// dynamic LDS carve (every offset a multiple of 16)
+constexpr int RC_OFF_CI = RC_UG * RC_CAP * 8;            // int32 [32][256] items
+constexpr int RC_OFF_THR = RC_OFF_CI + RC_UG * RC_CAP * 4;  // double [32] threshold scores
+constexpr int RC_OFF_SEEN = RC_OFF_THR + RC_UG * 8;      // uint64 [32] seen mask of the tile
+constexpr int RC_OFF_CUR = RC_OFF_SEEN + RC_UG * 8;      // int64 [32] seen-list cursor
+constexpr int RC_OFF_END = RC_OFF_CUR + RC_UG * 8;       // int64 [32] seen-list end
+constexpr int RC_OFF_THI = RC_OFF_END + RC_UG * 8;       // int32 [32] threshold item (−1: none)
+constexpr int RC_OFF_CNT = RC_OFF_THI + RC_UG * 4;       // int32 [32] candidates held
+constexpr int RC_OFF_TILE = RC_OFF_CNT + RC_UG * 4;
+static_assert(RC_OFF_TILE % 16 == 0);
+template <typename T>
+constexpr int rec_lds_bytes() {
+  return RC_OFF_TILE + RC_TI * RC_TS * (int)sizeof(T);
+}
+static_assert(rec_lds_bytes<double>() <= 160 * 1024);
+
+#pragma clang fp contract(off)
+__device__ __forceinline__ double mul_add_rn(double s, double a, double b) {
+  const double p = a * b;
+  return s + p;
+}
+#pragma clang fp contract(on)
+
+// (score a, item a) ranks before (score b, item b)
+__device__ __forceinline__ bool rec_before(double sa, int32_t ia, double sb, int32_t ib) {
+  return sa > sb || (sa == sb && ia < ib);
+}
+
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t uniform(int64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// One user's candidate list in LDS (RC_CAP entries), owned by one wave.
+struct RecList {
+  double* s;
+  int32_t* i;
+};
+
+// Appends the proposing lanes' (score, item) behind the `cnt` entries held; cnt + 64 ≤ RC_CAP.
+__device__ __forceinline__ int rec_append(RecList L, int cnt, bool propose, double s, int32_t item) {
+  const uint64_t m = __ballot(propose);
+  if (propose) {
+    const int slot = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                          __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    L.s[slot] = s;
+    L.i[slot] = item;
+  }
+  return cnt + (int)__popcll(m);
+}
+
+// Keeps the best min(cnt, topn) of the cnt ≤ RC_CAP entries, in rank order: every entry counts
+// the entries that rank before it (items are distinct, so the ranks are 0..cnt−1) and the
+// first topn move to their rank.  Every lane has read the whole list before the first store.
+__device__ __forceinline__ int rec_prune(RecList L, int cnt, int topn, int lane) {
+  double ms[RC_CAP / 64];
+  int32_t mi[RC_CAP / 64];
+  int rk[RC_CAP / 64];
+#pragma unroll
+  for (int r = 0; r < RC_CAP / 64; ++r) {
+    const int e = lane + 64 * r;
+    ms[r] = e < cnt ? L.s[e] : 0.0;
+    mi[r] = e < cnt ? L.i[e] : 0x7fffffff;
+    rk[r] = 0;
+  }
+  for (int j = 0; j < cnt; ++j) {
+    const double sj = L.s[j];
+    const int32_t ij = L.i[j];
+#pragma unroll
+    for (int r = 0; r < RC_CAP / 64; ++r) rk[r] += rec_before(sj, ij, ms[r], mi[r]) ? 1 : 0;
+  }
+#pragma unroll
+  for (int r = 0; r < RC_CAP / 64; ++r)
+    if (lane + 64 * r < cnt && rk[r] < topn) {
+      L.s[rk[r]] = ms[r];
+      L.i[rk[r]] = mi[r];
+    }
+  return cnt < topn ? cnt : topn;
+}
+
+// Lanes 0..c−1 hold the ascending window entries v; is `item` among them?  (binary search
+// with lane shuffles; c in 1..64, wave-uniform)
+__device__ __forceinline__ bool rec_in_window(int32_t v, int c, int32_t item) {
+  int pos = 0;  // entries below item
+  for (int step = 1 << (31 - __clz(c)); step >= 1; step >>= 1) {
+    const int p = pos + step;
+    const int32_t vv = __shfl(v, (p - 1) & 63, 64);
+    if (p <= c && vv < item) pos = p;
+  }
+  const int32_t vp = __shfl(v, pos & 63, 64);
+  return pos < c && vp == item;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rec_users_kernel(RecArgs<T> a) {
+  // layout [t / 8][f][t % 8] (t relative to the batch's first user): one wave's 8 users at
+  // factor f are 64 contiguous bytes
+  const int64_t tr = blockIdx.x;
+  const int64_t t = a.t_base + tr;
+  const T* u = a.U + (t < a.nreq ? a.users[t] * (int64_t)a.kp : 0);
+  double* o = a.udbl + (tr / RC_UW) * a.k * RC_UW + (tr % RC_UW);
+  for (int f = threadIdx.x; f < a.k; f += blockDim.x)
+    o[f * RC_UW] = t < a.nreq ? (double)u[f] : 0.0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rec_select_kernel(RecArgs<T> a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* const cand_s = (double*)smem;
+  int32_t* const cand_i = (int32_t*)(smem + RC_OFF_CI);
+  double* const st_thr = (double*)(smem + RC_OFF_THR);
+  unsigned long long* const st_seen = (unsigned long long*)(smem + RC_OFF_SEEN);
+  int64_t* const st_cur = (int64_t*)(smem + RC_OFF_CUR);
+  int64_t* const st_end = (int64_t*)(smem + RC_OFF_END);
+  int32_t* const st_thi = (int32_t*)(smem + RC_OFF_THI);
+  int32_t* const st_cnt = (int32_t*)(smem + RC_OFF_CNT);
+  T* const tile = (T*)(smem + RC_OFF_TILE);
+
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t t0 = a.t_base + (int64_t)blockIdx.y * RC_UG;
+  const int64_t tw = t0 + w * RC_UW;  // first user of this wave
+  const int64_t i0 = (int64_t)blockIdx.x * a.chunk;
+  const int64_t i1 = i0 + a.chunk < a.nitems ? i0 + a.chunk : a.nitems;
+  // wave-uniform rows, read through the constant address space so they become scalar loads
+  typedef const __attribute__((address_space(4))) double* cdptr;
+  const cdptr ud = (cdptr)(a.udbl + (tw - a.t_base) * a.k);  // [f][8] for this wave's users
+
+  // The state of this wave's users (only this wave touches it, so no barrier orders it):
+  // an empty list without threshold, and the seen-list cursor at the chunk's first item.
+  if (lane < RC_UW) {
+    const int u = w * RC_UW + lane;
+    const int64_t t = tw + lane;
+    int64_t lo = 0, end = 0;
+    if (a.seen_ptr && t < a.nreq) {
+      const int64_t row = a.users[t];
+      lo = a.seen_ptr[row];
+      end = a.seen_ptr[row + 1];
+      int64_t hi = end;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)a.seen_col[mid] < i0)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+    }
+    st_cur[u] = lo;
+    st_end[u] = end;
+    st_cnt[u] = 0;
+    st_thi[u] = -1;
+    st_thr[u] = 0.0;
+    st_seen[u] = 0ull;
+  }
+
+  for (int64_t ib = i0; ib < i1; ib += RC_TI) {
+    const int64_t item = ib + lane;
+    const bool valid = item < i1;
+    const int32_t item32 = (int32_t)(uint32_t)item;
+    double acc[RC_UW];
+    const double b0 = (a.bias && valid) ? (double)a.bias[item] : 0.0;
+#pragma unroll
+    for (int g = 0; g < RC_UW; ++g) acc[g] = b0;
+    for (int f0 = 0; f0 < a.k; f0 += RC_KC) {
+      const int kc = a.k - f0 < RC_KC ? a.k - f0 : RC_KC;
+      __syncthreads();
+      for (int x = threadIdx.x; x < RC_TI * RC_KC; x += 256) {
+        const int r = x / RC_KC, cc = x - r * RC_KC;
+        tile[r * RC_TS + cc] = (ib + r < i1 && cc < kc) ? a.I[(ib + r) * a.kp + f0 + cc] : (T)0;
+      }
+      __syncthreads();
+      const T* q = &tile[lane * RC_TS];
+      const cdptr u0 = ud + f0 * RC_UW;
+      if (kc == RC_KC) {
+        // full stage, fully unrolled: every user value is an s_load at an immediate offset
+#pragma unroll
+        for (int f = 0; f < RC_KC; ++f) {
+          const double qf = (double)q[f];
+#pragma unroll
+          for (int g = 0; g < RC_UW; ++g) acc[g] = mul_add_rn(acc[g], u0[f * RC_UW + g], qf);
+        }
+      } else {
+        for (int f = 0; f < kc; ++f) {
+          const double qf = (double)q[f];
+#pragma unroll
+          for (int g = 0; g < RC_UW; ++g) acc[g] = mul_add_rn(acc[g], u0[f * RC_UW + g], qf);
+        }
+      }
+    }
+
+    // which of the tile's items each user has seen: the list entries below the tile's end
+    // (all ≥ ib: the cursor has passed everything below), 64 at a time, one per lane
+    if (a.seen_ptr) {
+      const int64_t iend = ib + RC_TI < i1 ? ib + RC_TI : i1;
+      for (int g = 0; g < RC_UW; ++g) {
+        const int u = w * RC_UW + g;
+        int64_t cur = uniform(st_cur[u]);
+        const int64_t end = uniform(st_end[u]);
+        bool seen = false;
+        for (;;) {
+          const int64_t e = cur + lane;
+          const int32_t v = e < end ? a.seen_col[e] : 0;
+          const int c = (int)__popcll(__ballot(e < end && (int64_t)v < iend));
+          if (c == 0) break;
+          seen = seen || rec_in_window(v, c, item32);
+          cur += c;
+          if (c < 64) break;
+        }
+        const unsigned long long m = __ballot(seen);
+        if (lane == 0) {
+          st_cur[u] = cur;
+          st_seen[u] = m;
+        }
+      }
+    }
+
+    // proposals: valid, unseen and ranking before the user's threshold
+#pragma unroll
+    for (int g = 0; g < RC_UW; ++g) {
+      if (tw + g >= a.nreq) break;  // uniform over the wave
+      const int u = w * RC_UW + g;
+      const int cnt = uniform(st_cnt[u]);
+      const int32_t thi = st_thi[u];
+      const double ths = st_thr[u];
+      const bool seen = (st_seen[u] >> lane) & 1ull;
+      const bool propose = valid && !seen && (thi < 0 || rec_before(acc[g], item32, ths, thi));
+      const RecList L{cand_s + u * RC_CAP, cand_i + u * RC_CAP};
+      const int n = rec_append(L, cnt, propose, acc[g], item32);
+      if (lane == 0) st_cnt[u] = n;
+    }
+
+    // a list that could not take another full tile, or holds N without a threshold yet, is
+    // pruned to the best N; a full list's last entry is the new threshold
+    for (int g = 0; g < RC_UW; ++g) {
+      const int u = w * RC_UW + g;
+      const int cnt = uniform(st_cnt[u]);
+      const int thi = uniform(st_thi[u]);
+      if (cnt > RC_CAP - RC_TI || (thi < 0 && cnt >= a.topn)) {
+        const RecList L{cand_s + u * RC_CAP, cand_i + u * RC_CAP};
+        const int n = rec_prune(L, cnt, a.topn, lane);
+        if (lane == 0) {
+          st_cnt[u] = n;
+          if (n == a.topn) {
+            st_thr[u] = L.s[n - 1];
+            st_thi[u] = L.i[n - 1];
+          }
+        }
+      }
+    }
+  }
+
+  // the chunk's survivors in rank order → [chunk][user of the batch][topn]
+  for (int g = 0; g < RC_UW; ++g) {
+    if (tw + g >= a.nreq) break;
+    const int u = w * RC_UW + g;
+    const RecList L{cand_s + u * RC_CAP, cand_i + u * RC_CAP};
+    const int n = rec_prune(L, uniform(st_cnt[u]), a.topn, lane);
+    const int64_t slot = (int64_t)blockIdx.x * a.nbatch + (tw + g - a.t_base);
+    for (int j = lane; j < n; j += 64) {
+      a.part_score[slot * a.topn + j] = L.s[j];
+      a.part_item[slot * a.topn + j] = L.i[j];
+    }
+    if (lane == 0) a.part_cnt[slot] = n;
+  }
+}
+
+struct RecMergeArgs {
+  const double* part_score;
+  const int32_t* part_item;
+  const int32_t* part_cnt;
+  int64_t nchunk, nbatch, t_base, nreq;
+  int topn;
+  int64_t* items;
+  double* scores;
+  int32_t* counts;
+};
+
+__global__ __launch_bounds__(64) void rec_merge_kernel(RecMergeArgs a) {
+  __shared__ double ls[RC_CAP];
+  __shared__ int32_t li[RC_CAP];
+  const int lane = threadIdx.x;
+  const int64_t tr = blockIdx.x;
+  const int64_t t = a.t_base + tr;
+  if (t >= a.nreq) return;
+  const RecList L{ls, li};
+  int cnt = 0;
+  int32_t thi = -1;
+  double ths = 0.0;
+  // the chunks' slots [chunk][topn] as one list, 64 slots at a time
+  const int64_t total = a.nchunk * a.topn;
+  for (int64_t e0 = 0; e0 < total; e0 += 64) {
+    const int64_t e = e0 + lane;
+    bool valid = e < total;
+    double s = 0.0;
+    int32_t it = 0;
+    if (valid) {
+      const int64_t ch = e / a.topn;
+      const int64_t j = e - ch * a.topn;
+      const int64_t slot = ch * a.nbatch + tr;
+      valid = j < a.part_cnt[slot];
+      if (valid) {
+        s = a.part_score[slot * a.topn + j];
+        it = a.part_item[slot * a.topn + j];
+      }
+    }
+    const bool propose = valid && (thi < 0 || rec_before(s, it, ths, thi));
+    cnt = uniform(rec_append(L, cnt, propose, s, it));
+    if (cnt > RC_CAP - 64 || (thi < 0 && cnt >= a.topn)) {
+      cnt = rec_prune(L, cnt, a.topn, lane);
+      if (cnt == a.topn) {
+        ths = L.s[cnt - 1];
+        thi = L.i[cnt - 1];
+      }
+    }
+  }
+  cnt = rec_prune(L, cnt, a.topn, lane);
+  for (int j = lane; j < a.topn; j += 64) {
+    a.items[t * a.topn + j] = j < cnt ? (int64_t)L.i[j] : -1;
+    a.scores[t * a.topn + j] = j < cnt ? L.s[j] : 0.0;
+  }
+  if (lane == 0) a.counts[t] = cnt;
+}
+
+template <typename T>
+hipError_t recommend(const RecArgs<T>& a0, hipStream_t s) {
+  if (a0.k > RC_KMAX || a0.topn < 1 || a0.topn > kRecMaxN) return hipErrorInvalidValue;
+  if (a0.nreq == 0) return hipSuccess;
+  RecArgs<T> a = a0;
+  // above 64 KiB of LDS: dynamic shared memory with the function's limit raised
+  hipError_t e = hipFuncSetAttribute((const void*)rec_select_kernel<T>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     rec_lds_bytes<T>());
+  if (e != hipSuccess) return e;
+  const int64_t groups = (a.nreq + RC_UG - 1) / RC_UG;
+  const int64_t nchunk = eval_chunks(a.nreq, a.nitems);
+  a.chunk = ((a.nitems + nchunk - 1) / nchunk + RC_TI - 1) / RC_TI * RC_TI;
+  // users in batches of eval_batch_groups() groups (grid.y ≤ 65535; the users' fp64 rows and
+  // the partial lists are staged per batch)
+  const int64_t bg = eval_batch_groups();
+  for (int64_t g0 = 0; g0 < groups; g0 += bg) {
+    const int64_t ng = groups - g0 < bg ? groups - g0 : bg;
+    a.t_base = g0 * RC_UG;
+    a.nbatch = ng * RC_UG;
+    const int64_t nu = a.nreq - a.t_base < a.nbatch ? a.nreq - a.t_base : a.nbatch;
+    hipLaunchKernelGGL(rec_users_kernel<T>, dim3((unsigned)a.nbatch), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(rec_select_kernel<T>, dim3((unsigned)nchunk, (unsigned)ng), dim3(256),
+                       rec_lds_bytes<T>(), s, a);
+    const RecMergeArgs m{a.part_score, a.part_item, a.part_cnt, nchunk, a.nbatch, a.t_base,
+                         a.nreq,       a.topn,      a.items,    a.scores, a.counts};
+    hipLaunchKernelGGL(rec_merge_kernel, dim3((unsigned)nu), dim3(64), 0, s, m);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+}  // namespace
+
+hipError_t launch_recommend(const RecArgs<float>& a, hipStream_t s) { return recommend(a, s); }
+hipError_t launch_recommend(const RecArgs<double>& a, hipStream_t s) { return recommend(a, s); }
+
+}  // namespace qmfx

@@ -31,8 +31,24 @@ class Engine {
   virtual void evaluate(const size_t epoch) {}
   virtual void saveUserFactors(const std::string& fileName) const {}
   virtual void saveItemFactors(const std::string& fileName) const {}
+  // Addition to the reference API: the topN (1..QMFX_REC_MAX_N) best items of every training
+  // user (ascending user idx), or of the users in `userIds` in that order (unknown ids are
+  // skipped with one warning), selected on the device from the current factors.  One line
+  // "<userId> <itemId> <score>\n" per pair, scores with 9 decimals, each user's lines in rank
+  // order (higher score first, equal scores by ascending item idx): the dataset format, so
+  // DatasetReader reads the file back.  includeSeen = false leaves the user's training items
+  // out; a user with no eligible item writes nothing.
+  virtual void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
+                                       const std::vector<int64_t>* userIds = nullptr) const {}
 
  protected:
+  // saveUserRecommendations of the engines: qmfx_recommend (include/qmfx.h) with the given
+  // exclude mode in batches of at most 65,536 users, formatted and written batch by batch
+  static void saveRecommendations(qmfx_ctx* ctx, int exclude, bool useBiases,
+                                  const IdIndex& userIndex, const IdIndex& itemIndex,
+                                  const std::string& fileName, size_t topN,
+                                  const std::vector<int64_t>* userIds);
+
   // test users (those with at least one known (user, item) test pair), optionally a
   // sample of numTestUsers of them shuffled with mt19937(seed), and their dense label rows
   static void initAvgTestData(std::vector<size_t>& testUsers,

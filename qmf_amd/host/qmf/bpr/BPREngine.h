@@ -59,6 +59,10 @@ class BPREngine : public Engine {
 
   void saveUserFactors(const std::string& fileName) const override;
   void saveItemFactors(const std::string& fileName) const override;
+  // includeSeen = false leaves out the user's training positives; scores include the item
+  // biases when the model uses them
+  void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
+                               const std::vector<int64_t>* userIds = nullptr) const override;
 
   // --- additions (not in the reference API) ---
   struct PosNegTriplet {

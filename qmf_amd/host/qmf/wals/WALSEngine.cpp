@@ -180,6 +180,16 @@ void WALSEngine::saveItemFactors(const std::string& fileName) const {
   saveFactors(itemFactors(), itemIndex_, fileName);
 }
 
+void WALSEngine::saveUserRecommendations(const std::string& fileName, const size_t topN,
+                                         const bool includeSeen,
+                                         const std::vector<int64_t>* userIds) const {
+  CHECK(dev_) << "no factor data, have you initialized the engine?";
+  // a rank holds only its own users' signals; routing users to their rank is not built
+  CHECK_EQ(ranks_.size(), 1u) << "recommendations need --ngpus=1";
+  saveRecommendations(dev_->get(), includeSeen ? QMFX_REC_ALL : QMFX_REC_UNSEEN_SIGNALS, false,
+                      userIndex_, itemIndex_, fileName, topN, userIds);
+}
+
 size_t WALSEngine::nusers() const { return userIndex_.size(); }
 size_t WALSEngine::nitems() const { return itemIndex_.size(); }
 

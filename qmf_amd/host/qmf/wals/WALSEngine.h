@@ -50,6 +50,9 @@ class WALSEngine : public Engine {
 
   void saveUserFactors(const std::string& fileName) const override;
   void saveItemFactors(const std::string& fileName) const override;
+  // includeSeen = false leaves out the items of the user's training signals (one GPU only)
+  void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
+                               const std::vector<int64_t>* userIds = nullptr) const override;
 
   // --- additions (not in the reference API) ---
   // host copies of the current factors (synchronised from the device on access)

@@ -1,6 +1,10 @@
 // `bpr` command line, drop-in for the reference's qmf/bpr.cpp:28-125: same flags, same log
 // lines and output files.  Additions: --device, --precision (32 | 64), --seed (0 keeps the
-// reference's random_device seeding).
+// reference's random_device seeding), and the top-N recommendations of the trained model:
+// --user_recommendations, --num_recommendations, --recommend_seen, --recommend_users.
+#include <chrono>
+#include <cstdlib>
+#include <fstream>
 #include <memory>
 
 #include <qmf/DatasetReader.h>
@@ -44,6 +48,12 @@ DEFINE_bool(test_always, false,
 // model output
 DEFINE_string(user_factors, "", "filename of user factors");
 DEFINE_string(item_factors, "", "filename of item factors");
+// recommendations
+DEFINE_string(user_recommendations, "", "filename of the users' top-N recommendations");
+DEFINE_uint64(num_recommendations, 10, "items recommended per user (1..128)");
+DEFINE_bool(recommend_seen, false, "also recommend items of the user's training data");
+DEFINE_string(recommend_users, "",
+              "file with one user id per line to recommend for (default: every training user)");
 
 int main(int argc, char** argv) {
   if (!qmf::flags::parse(&argc, &argv, "bpr")) return 1;
@@ -67,6 +77,9 @@ int main(int argc, char** argv) {
   for (const auto& metric : qmf::split(FLAGS_test_avg_metrics, ',')) {
     CHECK(metricsEngine->addTestAvgMetric(metric)) << "metric " << metric << " is not available";
   }
+  if (!FLAGS_user_recommendations.empty())
+    CHECK(FLAGS_num_recommendations >= 1 && FLAGS_num_recommendations <= QMFX_REC_MAX_N)
+        << "--num_recommendations must be in 1.." << QMFX_REC_MAX_N;
   qmf::DeviceOptions device;
   device.device = FLAGS_device;
   device.precision = FLAGS_precision;
@@ -88,6 +101,23 @@ int main(int argc, char** argv) {
     LOG(INFO) << "saving model output";
     engine.saveUserFactors(FLAGS_user_factors);
     engine.saveItemFactors(FLAGS_item_factors);
+  }
+  if (!FLAGS_user_recommendations.empty()) {
+    LOG(INFO) << "saving recommendations";
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int64_t> ids;
+    if (!FLAGS_recommend_users.empty()) ids = qmf::readIds(FLAGS_recommend_users);
+    engine.saveUserRecommendations(FLAGS_user_recommendations, FLAGS_num_recommendations,
+                                   FLAGS_recommend_seen,
+                                   FLAGS_recommend_users.empty() ? nullptr : &ids);
+    // QMF_TIMINGS=1 (an addition, as in wals): the phase's wall time
+    const char* tm = std::getenv("QMF_TIMINGS");
+    if (tm && std::atoi(tm) > 0) {
+      std::ifstream f(FLAGS_user_recommendations, std::ios::binary | std::ios::ate);
+      LOG(INFO) << "timing: recommend "
+                << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                << " s, " << (f ? static_cast<long long>(f.tellg()) : 0) << " bytes";
+    }
   }
   return 0;
 }

@@ -1,5 +1,7 @@
 // `wals` command line, drop-in for the reference's qmf/wals.cpp:26-107: same flags, same
-// log lines and output files.  Additions: --device, --precision (32 | 64), --ngpus.
+// log lines and output files.  Additions: --device, --precision (32 | 64), --ngpus, and the
+// top-N recommendations of the trained model: --user_recommendations, --num_recommendations,
+// --recommend_seen, --recommend_users.
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -40,6 +42,12 @@ DEFINE_bool(test_always, false,
 // model output
 DEFINE_string(user_factors, "", "filename of user factors");
 DEFINE_string(item_factors, "", "filename of item factors");
+// recommendations
+DEFINE_string(user_recommendations, "", "filename of the users' top-N recommendations");
+DEFINE_uint64(num_recommendations, 10, "items recommended per user (1..128)");
+DEFINE_bool(recommend_seen, false, "also recommend items of the user's training data");
+DEFINE_string(recommend_users, "",
+              "file with one user id per line to recommend for (default: every training user)");
 
 namespace {
 // QMF_TIMINGS=1 (an addition; unset, the output is the reference's): one "timing:" log line per
@@ -73,6 +81,9 @@ int main(int argc, char** argv) {
   for (const auto& metric : qmf::split(FLAGS_test_avg_metrics, ',')) {
     CHECK(metricsEngine->addTestAvgMetric(metric)) << "metric " << metric << " is not available";
   }
+  if (!FLAGS_user_recommendations.empty())
+    CHECK(FLAGS_num_recommendations >= 1 && FLAGS_num_recommendations <= QMFX_REC_MAX_N)
+        << "--num_recommendations must be in 1.." << QMFX_REC_MAX_N;
   qmf::DeviceOptions device;
   device.device = FLAGS_device;
   device.precision = FLAGS_precision;
@@ -108,6 +119,18 @@ int main(int argc, char** argv) {
     if (timings())
       LOG(INFO) << "timing: save " << now() - t0 << " s, "
                 << fileBytes(FLAGS_user_factors) + fileBytes(FLAGS_item_factors) << " bytes";
+  }
+  if (!FLAGS_user_recommendations.empty()) {
+    LOG(INFO) << "saving recommendations";
+    t0 = now();
+    std::vector<int64_t> ids;
+    if (!FLAGS_recommend_users.empty()) ids = qmf::readIds(FLAGS_recommend_users);
+    engine.saveUserRecommendations(FLAGS_user_recommendations, FLAGS_num_recommendations,
+                                   FLAGS_recommend_seen,
+                                   FLAGS_recommend_users.empty() ? nullptr : &ids);
+    if (timings())
+      LOG(INFO) << "timing: recommend " << now() - t0 << " s, "
+                << fileBytes(FLAGS_user_recommendations) << " bytes";
   }
   return 0;
 }
