@@ -13,6 +13,7 @@
 // order matches BPREngine::update exactly (p_u from the old q, q_i / q_n from the new p_u).
 #include "common.h"
 #include "kernels.h"
+#include "ntswitch.h"
 #include "rowsolve.h"
 
 namespace qmfx {
@@ -401,17 +402,6 @@ __global__ void sum_partials_kernel(const double* partial, int n, double* out) {
     default: return hipErrorInvalidValue; \
   }
 
-#define QMFX_NT_SWITCH(KP, CALL)                                            \
-  switch ((KP) / 16) {                                                      \
-    case 1: return CALL(1);   case 2: return CALL(2);   case 3: return CALL(3);   \
-    case 4: return CALL(4);   case 5: return CALL(5);   case 6: return CALL(6);   \
-    case 7: return CALL(7);   case 8: return CALL(8);   case 9: return CALL(9);   \
-    case 10: return CALL(10); case 11: return CALL(11); case 12: return CALL(12); \
-    case 13: return CALL(13); case 14: return CALL(14); case 15: return CALL(15); \
-    case 16: return CALL(16);                                               \
-    default: return hipErrorInvalidValue;                                   \
-  }
-
 template <typename T, int E>
 static hipError_t bpr_epoch(const BprArgs<T>& a, hipStream_t s) {
   if (a.capped)
@@ -462,16 +452,18 @@ hipError_t launch_bpr_apply(const BprArgs<double>& a, const int64_t* trip, int64
 hipError_t launch_bpr_eval(const float* U, const float* I, const float* bias,
                            const int64_t* trip, int64_t n, int kp, int use_biases,
                            double* partial, double* out, hipStream_t s) {
-#define CALL(NT) bpr_eval<float, NT>(U, I, bias, trip, n, kp, use_biases, partial, out, s)
-  QMFX_NT_SWITCH(kp, CALL)
-#undef CALL
+  return dispatch_nt<1, 16>(kp / 16, [&](auto N) {
+    return bpr_eval<float, decltype(N)::value>(U, I, bias, trip, n, kp, use_biases, partial, out,
+                                               s);
+  });
 }
 hipError_t launch_bpr_eval(const double* U, const double* I, const double* bias,
                            const int64_t* trip, int64_t n, int kp, int use_biases,
                            double* partial, double* out, hipStream_t s) {
-#define CALL(NT) bpr_eval<double, NT>(U, I, bias, trip, n, kp, use_biases, partial, out, s)
-  QMFX_NT_SWITCH(kp, CALL)
-#undef CALL
+  return dispatch_nt<1, 16>(kp / 16, [&](auto N) {
+    return bpr_eval<double, decltype(N)::value>(U, I, bias, trip, n, kp, use_biases, partial,
+                                                out, s);
+  });
 }
 
 }  // namespace qmfx

@@ -116,13 +116,10 @@ __device__ __forceinline__ void fmac_bcast16(float& acc, float src, float m) {
 // 1/d for the LDLᵀ pivots: fp32 v_rcp_f32 (1 ulp); fp64 v_rcp_f64 + two Newton steps (an ulp
 // or so; a non-positive or NaN d leaves the result outside (0, ∞), which the caller flags)
 __device__ __forceinline__ float pivot_rcp(float d) { return __builtin_amdgcn_rcpf(d); }
-#ifndef QMFX_RCP_NEWTON
-#define QMFX_RCP_NEWTON 2
-#endif
 __device__ __forceinline__ double pivot_rcp(double d) {
   double r = __builtin_amdgcn_rcp(d);
 #pragma unroll
-  for (int i = 0; i < QMFX_RCP_NEWTON; ++i) {
+  for (int i = 0; i < 2; ++i) {
     const double e = __builtin_fma(-d, r, 1.0);
     r = __builtin_fma(r, e, r);
   }
@@ -216,9 +213,6 @@ __device__ __forceinline__ void chol_solve(typename Mfma<T>::acc_t (&acc)[NT * (
   const int cl = lane & 15;
   const int kk = lane >> 4;
   const int q0 = DG ? 16 : 0;  // first panel row held by slot 0
-#ifdef QMFX_DEBUG
-  if (blockDim.x * blockDim.y * blockDim.z != 64) __builtin_trap();  // single-wave callers only
-#endif
 #pragma unroll
   for (int p = 0; p < NT; ++p) {
     const int R = KP - 16 * p;

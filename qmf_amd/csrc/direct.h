@@ -45,12 +45,6 @@ struct Perm {
 // so they add exactly nothing and need no masking.  Σc is summed at staging.  Pipeline:
 // the rows of step s+1 are in flight while step s's MFMAs run.  A negative weight (1 + αv
 // may still be > 0) sets `negw`; the caller flags the row for the host solve.
-#ifndef QMFX_GRAM_HEAD
-#define QMFX_GRAM_HEAD 100
-#endif
-#ifndef QMFX_GRAM_VALU
-#define QMFX_GRAM_VALU 2
-#endif
 template <int NT>
 __device__ __forceinline__ void gram_split_bf16(const SolveArgs<float>& a, int64_t beg,
                                                 int64_t end, f32x4 (&acc)[NT * (NT + 1) / 2],
@@ -165,11 +159,12 @@ __device__ __forceinline__ void gram_split_bf16(const SolveArgs<float>& a, int64
     }
     // issue order: the sqrt/rhs VALU and block 0's split up front, then one MFMA and two
     // VALU at a time (an MFMA holds the vector issue for 8 of its 16 cycles)
-    __builtin_amdgcn_sched_group_barrier(0x2, QMFX_GRAM_HEAD, 0);
+    constexpr int HEAD_VALU = 100, VALU_PER_MFMA = 2;
+    __builtin_amdgcn_sched_group_barrier(0x2, HEAD_VALU, 0);
 #pragma unroll
     for (int i = 0; i < 6 * NT * (NT + 1) / 2; ++i) {
       __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x2, QMFX_GRAM_VALU, 0);
+      __builtin_amdgcn_sched_group_barrier(0x2, VALU_PER_MFMA, 0);
     }
   };
   int col0[8];
@@ -188,33 +183,20 @@ __device__ __forceinline__ void gram_split_bf16(const SolveArgs<float>& a, int64
 }
 
 // fp64 k = 112 / 128 direct Gram: the accumulator tiles are pinned to a register class by
-// issuing the MFMA from inline asm — the first QMFX_F64_AG tiles in AGPRs (srcC / vdst may be
+// issuing the MFMA from inline asm — the first kF64AgprTiles tiles in AGPRs (srcC / vdst may be
 // AGPRs at full rate), the rest in VGPRs, so the step's rows, w·y and rhs stay in VGPRs.  With
 // the builtin the allocator put 27 tiles in VGPRs and 9 in AGPRs, landed the gathered rows in
 // AGPRs and copied them (and one rotating tile) through v_accvgpr moves at every step
 // boundary.  The asm is opaque to the hazard recognizer: each MFMA carries its own 2 wait
 // states for a VALU-written srcA/B/C (issued while the previous MFMA holds the pipe), and the
 // loop's exit pads the f64 MFMA → VALU/VMEM read distance (gram_asm_drain).
-#ifndef QMFX_F64_ASM
-#define QMFX_F64_ASM 1
-#endif
 // Wait states the asm relies on (gfx950, MI355X_MICROARCH / the ISA's MFMA hazard table): a
 // VALU write of an MFMA's srcA/B/C needs 2 before the MFMA (the `s_nop 1` in front of each
 // asm MFMA; it issues while the previous MFMA holds the pipe); an f64 16x16x4 MFMA's result
 // read by VALU / VMEM / a non-dependent MFMA needs up to 18 (gram_asm_drain's 3 × s_nop 7 at the
 // loop exit).  tests/test_isa.py checks the compiled Gram loop: MFMAs only on pinned tiles,
 // no v_accvgpr moves or scratch between them.
-#ifndef QMFX_F64_AG
-#define QMFX_F64_AG 24
-#endif
-// fp64 k > 64 row solves run gram_plain (DPP-broadcast signal pairs, a ring of PD row buffers)
-// the ring depth of the other gram_plain instances (fp32 k ≤ 80, fp64 k ≤ 64)
-#ifndef QMFX_PLAIN_PD
-#define QMFX_PLAIN_PD 4
-#endif
-#ifndef QMFX_F64_PD
-#define QMFX_F64_PD 2
-#endif
+constexpr int kF64AgprTiles = 24;
 template <bool AG>
 __device__ __forceinline__ void mfma_f64_pinned(f64x4& c, double x, double y) {
   if constexpr (AG)
@@ -225,7 +207,7 @@ __device__ __forceinline__ void mfma_f64_pinned(f64x4& c, double x, double y) {
 template <int i, int NTT>
 __device__ __forceinline__ void pin_tiles(f64x4 (&acc)[NTT]) {
   if constexpr (i < NTT) {
-    if constexpr (i < QMFX_F64_AG)
+    if constexpr (i < kF64AgprTiles)
       asm volatile("" : "+a"(acc[i]));
     else
       asm volatile("" : "+v"(acc[i]));
@@ -243,7 +225,7 @@ __device__ __forceinline__ void gram_step_pinned(f64x4 (&acc)[NTT], const double
                                                  const double (&wy)[NT]) {
   if constexpr (i < NTT) {
     constexpr int I = tile_row(i), J = i - I * (I + 1) / 2;
-    mfma_f64_pinned<(i < QMFX_F64_AG)>(acc[i], yv[I], wy[J]);
+    mfma_f64_pinned<(i < kF64AgprTiles)>(acc[i], yv[I], wy[J]);
     gram_step_pinned<i + 1, NTT, NT>(acc, yv, wy);
   }
 }
@@ -261,11 +243,11 @@ __device__ __forceinline__ void gram_step_pinned(f64x4 (&acc)[NTT], const double
 // chunk's (column, value) pairs are loaded a whole chunk ahead.
 template <typename T, int NT>
 constexpr int plain_depth() {
-  // fp64 k = 80..128 row and heavy-row solves: a ring of QMFX_F64_PD = 2 (the pinned
+  // fp64 k = 80..128 row and heavy-row solves: a ring of 2 (the pinned
   // accumulators leave room for two row buffers: round 5, profiles/r05/ab_f64_pinned_gram_c3.txt,
   // 189.0 -> 180.0 ms per C3 item half); the one-step loop below remains only for the split-K
-  // segment instance (MODE 1)
-  return (sizeof(T) == 8 && NT > 4) ? QMFX_F64_PD : QMFX_PLAIN_PD;
+  // segment instance (MODE 1).  The other gram_plain instances (fp32 k ≤ 80, fp64 k ≤ 64): 4
+  return (sizeof(T) == 8 && NT > 4) ? 2 : 4;
 }
 template <int J>
 __device__ __forceinline__ int row_bcast(int v) {
@@ -291,7 +273,7 @@ __device__ __forceinline__ void gram_plain(const SolveArgs<T>& a, int64_t beg, i
                                            T (&bpart)[NT], double& csum, int lane) {
   using M = Mfma<T>;
   constexpr int KP = 16 * NT;
-  constexpr bool ASM = QMFX_F64_ASM && sizeof(T) == 8 && NT * (NT + 1) / 2 > 21;
+  constexpr bool ASM = sizeof(T) == 8 && NT * (NT + 1) / 2 > 21;
   static_assert(16 % PD == 0, "the ring must tile a chunk");
   const int cl = lane & 15;
   const int g = lane >> 4;
@@ -423,9 +405,6 @@ __device__ __forceinline__ void gram_plain(const SolveArgs<T>& a, int64_t beg, i
 // descriptor measured slower: the trace showed the gathers' latency is a small part of a
 // row, and a fixed grid loses the dispatcher's balancing.)
 // ---------------------------------------------------------------------------------------
-#ifndef QMFX_WAVES_NT8
-#define QMFX_WAVES_NT8 1
-#endif
 // waves per SIMD the direct kernel is compiled for: fp32 split-Gram and fp64 k > 64 tilings
 // keep their accumulators in the whole (VGPR + AGPR) register file of one wave
 template <typename T, int NT>
@@ -433,7 +412,8 @@ constexpr int direct_waves() {
   // fp64 k = 48 / 64: 3 / 2 waves (asked for 4, the row solve settled there anyway and the
   // split-K segment instance spilled 896 VGPRs)
   if constexpr (sizeof(T) == 8 && NT >= 3 && NT <= 4) return NT == 3 ? 3 : 2;
-  return Perm<NT>::template split<T> ? QMFX_WAVES_NT8 : (sizeof(T) == 8 && NT > 4 ? 1 : (NT <= 4 ? 4 : 2));
+  constexpr int SPLIT_WAVES = 1;  // the split-bf16 tilings (fp32 k ≥ 96), see the kernel's head
+  return Perm<NT>::template split<T> ? SPLIT_WAVES : (sizeof(T) == 8 && NT > 4 ? 1 : (NT <= 4 ? 4 : 2));
 }
 
 // MODE (compile time, so the row-solve instance keeps its register allocation): 0 = row
@@ -442,7 +422,7 @@ template <typename T, int NT, bool TRACE, int MODE = 0>
 __global__ __launch_bounds__(64, (direct_waves<T, NT>()))
 void wals_direct_kernel(SolveArgs<T> a) {
   // fp32 at NT = 8: the split-bf16 Gram keeps 144 accumulator + 96 operand + 128 row
-  // registers live: one wave per SIMD with the whole register file (QMFX_WAVES_NT8 = 1)
+  // registers live: one wave per SIMD with the whole register file (direct_waves)
   using M = Mfma<T>;
   using acc_t = typename M::acc_t;
   constexpr int KP = 16 * NT;
@@ -526,7 +506,6 @@ void wals_direct_kernel(SolveArgs<T> a) {
       // validity)
       // (the split-K segment instance keeps the builtin: pinned, its zero-initialised tiles
       // and the partial-image stores spilled 208 VGPRs)
-      constexpr bool ASM = QMFX_F64_ASM && NTT > 21 && MODE != 1;
       for (int64_t base = beg; base < end; base += 64) {
         const int nst = (int)(end - base < 64 ? end - base : 64);
         const int cr = lane < nst ? a.col[base + lane] : a.zrow;
@@ -559,24 +538,16 @@ void wals_direct_kernel(SolveArgs<T> a) {
 #pragma unroll
           for (int q = 0; q < NT; ++q) bpart[q] += cw * yv[q];
           csum += (double)cw;
-          if constexpr (ASM) {
-            T wy[NT];
 #pragma unroll
-            for (int q = 0; q < NT; ++q) wy[q] = w * yv[q];
-            gram_step_pinned<0, NTT, NT>(acc, yv, wy);
-          } else {
+          for (int I = 0; I < NT; ++I) {
 #pragma unroll
-            for (int I = 0; I < NT; ++I) {
-#pragma unroll
-              for (int J = 0; J <= I; ++J) {
-                const int t = tile_index(I, J);
-                acc[t] = M::mma(yv[I], w * yv[J], acc[t]);
-              }
+            for (int J = 0; J <= I; ++J) {
+              const int t = tile_index(I, J);
+              acc[t] = M::mma(yv[I], w * yv[J], acc[t]);
             }
           }
         }
       }
-      if constexpr (ASM) gram_asm_drain<NTT>(acc);
     } else {
       gram_plain<T, NT, plain_depth<T, NT>()>(a, beg, (int)(end - beg), acc, bpart, csum, lane);
     }

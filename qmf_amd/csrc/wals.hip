@@ -25,7 +25,8 @@
 // This file: YᵀY, the G + λI tile image of the direct kernel, the fixed-order loss sum and
 // the MFMA layout self-test.  The direct row kernel is csrc/direct.h (instantiated by
 // wals_direct_f32.hip / wals_direct_f64.hip / wals_heavy.hip), the whitened kernels
-// woodbury.hip, the multi-wave k > 128 row kernel wals_big.hip, its tiled YᵀY gram_big.hip.
+// woodbury.hip (their whitening GEMMs whiten.hip, the L⁻¹ behind them chol_inv.hip), the
+// multi-wave k > 128 row kernel wals_big.hip, its tiled YᵀY gram_big.hip.
 #include "direct.h"
 #include "gram_reduce.h"
 
@@ -179,27 +180,27 @@ static hipError_t launch_gram_nt(const T* Y, int64_t n, T* G, double* partial,
 }
 
 hipError_t launch_gimg(const float* G, int nt, int k, double lambda, float* img, hipStream_t s) {
-#define CALL(N) launch_gimg_nt<float, N>(G, k, lambda, img, s)
-  QMFX_NT_SWITCH(nt, CALL)
-#undef CALL
+  return dispatch_nt<1, 8>(nt, [&](auto N) {
+    return launch_gimg_nt<float, decltype(N)::value>(G, k, lambda, img, s);
+  });
 }
 hipError_t launch_gimg(const double* G, int nt, int k, double lambda, double* img,
                        hipStream_t s) {
-#define CALL(N) launch_gimg_nt<double, N>(G, k, lambda, img, s)
-  QMFX_NT_SWITCH(nt, CALL)
-#undef CALL
+  return dispatch_nt<1, 8>(nt, [&](auto N) {
+    return launch_gimg_nt<double, decltype(N)::value>(G, k, lambda, img, s);
+  });
 }
 hipError_t launch_gram(const float* Y, int64_t n, int nt, float* G, double* partial,
                        int max_blocks, hipStream_t s) {
-#define CALL(N) launch_gram_nt<float, N>(Y, n, G, partial, max_blocks, s)
-  QMFX_NT_SWITCH(nt, CALL)
-#undef CALL
+  return dispatch_nt<1, 8>(nt, [&](auto N) {
+    return launch_gram_nt<float, decltype(N)::value>(Y, n, G, partial, max_blocks, s);
+  });
 }
 hipError_t launch_gram(const double* Y, int64_t n, int nt, double* G, double* partial,
                        int max_blocks, hipStream_t s) {
-#define CALL(N) launch_gram_nt<double, N>(Y, n, G, partial, max_blocks, s)
-  QMFX_NT_SWITCH64(nt, CALL)
-#undef CALL
+  return dispatch_nt<1, 4>(nt, [&](auto N) {
+    return launch_gram_nt<double, decltype(N)::value>(Y, n, G, partial, max_blocks, s);
+  });
 }
 
 // `out` must have room for kSumBlocks + 1 doubles: out[0] = sum, out[1..] = partials.

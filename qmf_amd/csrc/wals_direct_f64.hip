@@ -7,9 +7,8 @@ namespace qmfx {
 #ifndef QMFX_KERNELS_ONLY
 hipError_t launch_wals_direct(const SolveArgs<double>& a, int nt, hipStream_t s) {
   if (a.seg_mode != 0) return launch_wals_heavy(a, nt, s);  // wals_heavy.hip
-#define CALL(N) launch_direct_mode<double, N, 0>(a, s)
-  QMFX_NT_SWITCH(nt, CALL)
-#undef CALL
+  return dispatch_nt<1, 8>(
+      nt, [&](auto N) { return launch_direct_mode<double, decltype(N)::value, 0>(a, s); });
 }
 #endif  // QMFX_KERNELS_ONLY
 

@@ -149,30 +149,26 @@ static hipError_t launch_heavy_reduce_nt(T* part, T* partb, double* partc, const
 }
 hipError_t launch_heavy_reduce(float* part, float* partb, double* partc, const int64_t* hseg,
                                int64_t h0, int64_t nh, const float* Gimg, int nt, hipStream_t s) {
-#define CALL(N) launch_heavy_reduce_nt<float, N>(part, partb, partc, hseg, h0, nh, Gimg, s)
-  QMFX_NT_SWITCH(nt, CALL)
-#undef CALL
+  return dispatch_nt<1, 8>(nt, [&](auto N) {
+    return launch_heavy_reduce_nt<float, decltype(N)::value>(part, partb, partc, hseg, h0, nh,
+                                                             Gimg, s);
+  });
 }
 hipError_t launch_heavy_reduce(double* part, double* partb, double* partc, const int64_t* hseg,
                                int64_t h0, int64_t nh, const double* Gimg, int nt, hipStream_t s) {
-#define CALL(N) launch_heavy_reduce_nt<double, N>(part, partb, partc, hseg, h0, nh, Gimg, s)
-  QMFX_NT_SWITCH(nt, CALL)
-#undef CALL
+  return dispatch_nt<1, 8>(nt, [&](auto N) {
+    return launch_heavy_reduce_nt<double, decltype(N)::value>(part, partb, partc, hseg, h0, nh,
+                                                              Gimg, s);
+  });
 }
 
 template <typename T>
 static hipError_t heavy_seg(const SolveArgs<T>& a, int nt, hipStream_t s) {
-#define CALL1(N) launch_direct_mode<T, N, 1>(a, s)
-#define CALL2(N) launch_direct_mode<T, N, 2>(a, s)
-  if (a.seg_mode == 1) {
-    QMFX_NT_SWITCH(nt, CALL1)
-  }
-  if (a.seg_mode == 2) {
-    QMFX_NT_SWITCH(nt, CALL2)
-  }
-#undef CALL1
-#undef CALL2
-  return hipErrorInvalidValue;
+  return dispatch_nt<1, 8>(nt, [&](auto N) {
+    if (a.seg_mode == 1) return launch_direct_mode<T, decltype(N)::value, 1>(a, s);
+    if (a.seg_mode == 2) return launch_direct_mode<T, decltype(N)::value, 2>(a, s);
+    return hipErrorInvalidValue;
+  });
 }
 hipError_t launch_wals_heavy(const SolveArgs<float>& a, int nt, hipStream_t s) {
   return heavy_seg(a, nt, s);

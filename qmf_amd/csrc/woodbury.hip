@@ -1,11 +1,9 @@
-// WALS whitened (n×n Woodbury) row kernels on MI355X (gfx950), the whitening GEMMs and the
-// fp64 inverse Cholesky factor of G + λI.  See wals.hip for the per-row algebra.
+// WALS whitened (n×n Woodbury) row kernels on MI355X (gfx950).  See wals.hip for the per-row
+// algebra, whiten.hip for the whitening GEMMs around them and chol_inv.hip for their L⁻¹.
 //
 // Reference path (taozhijiang/qmf): WALSEngine::updateFactorsForOne
 // qmf/wals/WALSEngine.cpp:266-310 and linearSymmetricSolve qmf/Matrix.cpp:81-96 (the same
 // solution by the push-through identity).
-#include <algorithm>
-#include <cstdlib>
 #include <type_traits>
 
 #include "chol.h"
@@ -261,34 +259,29 @@ __global__ __launch_bounds__(64, 2) void wals_woodbury_kernel(SolveArgs<double> 
 // rows were read a few µs earlier).  Lane (i, g) holds columns 32s + 8g .. +7 of signal
 // 16I + i in chunk s.  ≈150 VGPRs instead of 256 at NTN = 4: three waves per SIMD.
 // ---------------------------------------------------------------------------------------
-#ifndef QMFX_WB_ST_WAVES
-#define QMFX_WB_ST_WAVES 3
-#endif
 // K on the bf16 matrix cores from split3 parts (the exact f32 MFMA path measured slower at
 // k = 64 and 128: profiles/r06/ab_c2_f32_kpass.txt)
-// n×n buckets beyond 64 signals (NTN = 5..8, k = 256): each lane carries H = 2 signals (e
-// = lane and lane + 64); the registers of the wider tiles leave two or one waves per SIMD.
+// What the bucket n ≤ 16·NTN is compiled with.
 template <int NTN>
-constexpr int wb_st_waves() {
-  return NTN <= 4 ? QMFX_WB_ST_WAVES : (NTN == 5 ? 2 : 1);
-}
-// chunks in flight ahead of the one being consumed, K pass and x' pass (n ≤ 64 buckets)
-#ifndef QMFX_WBS_KD
-#define QMFX_WBS_KD 1
-#endif
-#ifndef QMFX_WBS_XD
-#define QMFX_WBS_XD 1
-#endif
-template <int NTN>
-constexpr int wbs_kdepth() {
-  return NTN <= 4 ? QMFX_WBS_KD : 1;
-}
-template <int NTN>
-constexpr int wbs_xdepth() {
-  return NTN <= 4 ? QMFX_WBS_XD : 1;
-}
+struct WbStCfg {
+  static_assert(NTN >= 1 && NTN <= 8);
+  //                                  NTN = 1  2  3  4  5  6  7  8
+  // waves per SIMD: the n×n buckets beyond 64 signals (NTN = 5..8, k = 128 / 256) carry H = 2
+  // signals per lane (e = lane and lane + 64), and the registers of the wider tiles leave
+  // two or one waves
+  static constexpr int WAVES_T[8] = {3, 3, 3, 3, 2, 1, 1, 1};
+  static constexpr int H_T[8]     = {1, 1, 1, 1, 2, 2, 2, 2};
+  // chunks in flight ahead of the one being consumed, K pass and x' pass
+  static constexpr int KD_T[8]    = {1, 1, 1, 1, 1, 1, 1, 1};
+  static constexpr int XD_T[8]    = {1, 1, 1, 1, 1, 1, 1, 1};
+  static constexpr int WAVES = WAVES_T[NTN - 1];
+  static constexpr int H = H_T[NTN - 1];
+  static constexpr int KD = KD_T[NTN - 1];
+  static constexpr int XD = XD_T[NTN - 1];
+};
 template <int NTK, int NTN>
-__global__ __launch_bounds__(64, wb_st_waves<NTN>()) void wals_woodbury_st_kernel(SolveArgs<float> a) {
+__global__ __launch_bounds__(64, WbStCfg<NTN>::WAVES) void wals_woodbury_st_kernel(SolveArgs<float> a) {
+  using C = WbStCfg<NTN>;
   using M = Mfma<float>;
   using acc_t = f32x4;
   constexpr int KP = 16 * NTK;
@@ -297,7 +290,7 @@ __global__ __launch_bounds__(64, wb_st_waves<NTN>()) void wals_woodbury_st_kerne
   __shared__ __attribute__((aligned(16))) CholShared<float, NTN> S;
   __shared__ __attribute__((aligned(16))) float gq[16 * NTN];
 
-  constexpr int H = NTN > 4 ? 2 : 1;  // signals per lane: e = lane + 64h
+  constexpr int H = C::H;  // signals per lane: e = lane + 64h
   const int lane = threadIdx.x;
   const int cl = lane & 15;
   const int kk = lane >> 4;
@@ -356,7 +349,7 @@ __global__ __launch_bounds__(64, wb_st_waves<NTN>()) void wals_woodbury_st_kerne
   for (int I = 0; I < NTN; ++I) sq[I] = 0.f;
   {
     // a ring of KD + 1 chunk buffers: chunk s + KD is in flight while chunk s is consumed
-    constexpr int KD = wbs_kdepth<NTN>();
+    constexpr int KD = C::KD;
     f32x4 buf[KD + 1][NTN][2];
 #pragma unroll
     for (int s = 0; s < KD && s < NS; ++s) load_chunk(s, buf[s]);
@@ -499,7 +492,7 @@ __global__ __launch_bounds__(64, wb_st_waves<NTN>()) void wals_woodbury_st_kerne
   // x' = Zₛᵀu (and for rows with Q signals xᵀb = x'ᵀ(Zₛᵀc)), the rows gathered again
   {
     // XD chunks in flight (the accumulators are dead after the solve)
-    constexpr int XD = wbs_xdepth<NTN>();
+    constexpr int XD = C::XD;
     f32x4 buf[XD + 1][NTN][2];
 #pragma unroll
     for (int s = 0; s < XD && s < NS; ++s) load_chunk(s, buf[s]);
@@ -561,93 +554,55 @@ __global__ __launch_bounds__(64, wb_st_waves<NTN>()) void wals_woodbury_st_kerne
 // ---------------------------------------------------------------------------------------
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
-// chunks in flight ahead of the one being consumed: K pass (beside the NTT accumulator
-// tiles) and x' pass (after the solve, when the accumulators are dead)
-#ifndef QMFX_WB64_KD
-#define QMFX_WB64_KD 1
-#endif
-// (x' pass: 2 since round 6, −0.9 ms per C3 fp64 user half same box, profiles/r06/
-// ab_whiten_lds.txt; round 3 had measured no gain with more chunks kept on chip)
-#ifndef QMFX_WB64_XD
-#define QMFX_WB64_XD 2
-#endif
-#ifndef QMFX_WB64_LTP
-#define QMFX_WB64_LTP 1
-#endif
-// waves per SIMD the streamed fp64 kernel is compiled for, by n×n tile count (n ≤ 16·NTN)
-#ifndef QMFX_WB64_WAVES
-#define QMFX_WB64_WAVES 2
-#endif
-#ifndef QMFX_WB64_WAVES3
-#define QMFX_WB64_WAVES3 2
-#endif
-#ifndef QMFX_WB64_WAVES2
-#define QMFX_WB64_WAVES2 2
-#endif
-template <int NTN>
-constexpr int wb64_waves() {
-  return NTN <= 2 ? QMFX_WB64_WAVES2 : NTN == 3 ? QMFX_WB64_WAVES3 : NTN == 4 ? QMFX_WB64_WAVES : 1;
-}
-template <int NTN>
-constexpr int wb64_kdepth() {
-  return NTN <= 4 ? QMFX_WB64_KD : 1;
-}
-// 16-column chunks of Zₛ kept in registers from the K pass to the x' pass (the first KEEP;
-// the rest are gathered again): the registers the n×n Cholesky leaves free at two waves per
-// SIMD (fp64 whitened rows are bound by the fabric's random-row rate, so every chunk not
-// re-gathered is 1/NTK of the second pass's bytes)
-// fp64 k = 64 whitened rows on the streamed kernel (round 5: C2 fp64 18.5 -> 17.6 ms/epoch
-// with n ≤ 48 whitened; the register-resident kernel measured slower there)
-#ifndef QMFX_WB64_KEEP2
-#define QMFX_WB64_KEEP2 6
-#endif
-#ifndef QMFX_WB64_KEEP3
-#define QMFX_WB64_KEEP3 2
-#endif
-#ifndef QMFX_WB64_KEEP4
-#define QMFX_WB64_KEEP4 1
-#endif
+// What the bucket n ≤ 16·NTN is compiled with at KP = 16·NTK.
 template <int NTK, int NTN>
-constexpr int wb64_keep() {
-  constexpr int k = NTN <= 2 ? QMFX_WB64_KEEP2 : NTN == 3 ? QMFX_WB64_KEEP3 : NTN == 4 ? QMFX_WB64_KEEP4 : 0;
-  return k < NTK ? k : NTK;
-}
-// and the next QMFX_WB64_KL{3,4,5} chunks kept in LDS (the room left under the per-CU LDS
-// at the kernel's waves per SIMD: ≤ 20 KB per row at n ≤ 64, ≤ 40 KB at n ≤ 80)
-#ifndef QMFX_WB64_KL3
-#define QMFX_WB64_KL3 1
-#endif
-#ifndef QMFX_WB64_KL4
-#define QMFX_WB64_KL4 1
-#endif
-#ifndef QMFX_WB64_KL5
-#define QMFX_WB64_KL5 2
-#endif
-template <int NTK, int NTN>
-constexpr int wb64_keep_lds() {
-  constexpr int k = NTN == 3 ? QMFX_WB64_KL3 : NTN == 4 ? QMFX_WB64_KL4 : NTN == 5 ? QMFX_WB64_KL5 : 0;
-  constexpr int room = NTK - wb64_keep<NTK, NTN>();
-  return k < room ? k : room;
-}
-template <int NTN>
-constexpr int wb64_xdepth() {
-  return NTN <= 4 ? QMFX_WB64_XD : 1;
-}
+struct Wb64Cfg {
+  static_assert(NTN >= 1 && NTN <= 5);
+  //                                  NTN = 1  2  3  4  5
+  // waves per SIMD, by n×n tile count
+  static constexpr int WAVES_T[5] = {2, 2, 2, 2, 1};
+  // signals per lane (e = lane + 64h)
+  static constexpr int H_T[5]     = {1, 1, 1, 1, 2};
+  // chunks in flight ahead of the one being consumed in the K pass (beside the NTT
+  // accumulator tiles)
+  static constexpr int KD_T[5]    = {1, 1, 1, 1, 1};
+  // and in the x' pass (after the solve, when the accumulators are dead): 2 since round 6,
+  // −0.9 ms per C3 fp64 user half same box, profiles/r06/ab_whiten_lds.txt; round 3 had
+  // measured no gain with more chunks kept on chip
+  static constexpr int XD_T[5]    = {2, 2, 2, 2, 1};
+  // 16-column chunks of Zₛ kept in registers from the K pass to the x' pass (the first KEEP;
+  // the rest are gathered again): the registers the n×n Cholesky leaves free at two waves per
+  // SIMD (fp64 whitened rows are bound by the fabric's random-row rate, so every chunk not
+  // re-gathered is 1/NTK of the second pass's bytes).  NTN ≤ 2: fp64 k = 64 whitened rows on
+  // the streamed kernel (round 5: C2 fp64 18.5 -> 17.6 ms/epoch with n ≤ 48 whitened; the
+  // register-resident kernel measured slower there)
+  static constexpr int KEEP_T[5]  = {6, 6, 2, 1, 0};
+  // and the next chunks kept in LDS (the room left under the per-CU LDS at the kernel's waves
+  // per SIMD: ≤ 20 KB per row at n ≤ 64, ≤ 40 KB at n ≤ 80)
+  static constexpr int KL_T[5]    = {0, 0, 1, 1, 2};
+  static constexpr int WAVES = WAVES_T[NTN - 1];
+  static constexpr int H = H_T[NTN - 1];
+  static constexpr int KD = KD_T[NTN - 1];
+  static constexpr int XD = XD_T[NTN - 1];
+  static constexpr int KEEP = KEEP_T[NTN - 1] < NTK ? KEEP_T[NTN - 1] : NTK;
+  static constexpr int KL = KL_T[NTN - 1] < NTK - KEEP ? KL_T[NTN - 1] : NTK - KEEP;
+};
 template <int NTK, int NTN, bool TRACE = false>
-__global__ __launch_bounds__(64, wb64_waves<NTN>()) void wals_woodbury_st64_kernel(SolveArgs<double> a) {
+__global__ __launch_bounds__(64, (Wb64Cfg<NTK, NTN>::WAVES)) void wals_woodbury_st64_kernel(SolveArgs<double> a) {
+  using C = Wb64Cfg<NTK, NTN>;
   using M = Mfma<double>;
   using acc_t = typename M::acc_t;
   constexpr int KP = 16 * NTK;
   constexpr int NTT = NTN * (NTN + 1) / 2;
   constexpr int NS = NTK;  // 16-column chunks
   // the diagonal L blocks ride in the panel array (chol.h, LTP): 10.8 KB per row at n ≤ 64
-  __shared__ __attribute__((aligned(16))) CholShared<double, NTN, QMFX_WB64_LTP != 0> S;
+  __shared__ __attribute__((aligned(16))) CholShared<double, NTN, true> S;
   __shared__ __attribute__((aligned(16))) double gq[16 * NTN];
   // Zₛ chunks kept in LDS for the x' pass: [chunk][I·4 + c][lane]
-  constexpr int KL = wb64_keep_lds<NTK, NTN>();
+  constexpr int KL = C::KL;
   __shared__ __attribute__((aligned(16))) double kl[KL > 0 ? KL : 1][NTN * 4][64];
 
-  constexpr int H = NTN > 4 ? 2 : 1;  // signals per lane: e = lane + 64h
+  constexpr int H = C::H;  // signals per lane: e = lane + 64h
   const int lane = threadIdx.x;
   const int cl = lane & 15;
   const int kk = lane >> 4;
@@ -697,7 +652,6 @@ __global__ __launch_bounds__(64, wb64_waves<NTN>()) void wals_woodbury_st64_kern
       buf[I][0] = u[0], buf[I][1] = u[1], buf[I][2] = v[0], buf[I][3] = v[1];
     }
   };
-  auto load_chunk_x = load_chunk;
 
   acc_t acc[NTT];
 #pragma unroll
@@ -705,12 +659,12 @@ __global__ __launch_bounds__(64, wb64_waves<NTN>()) void wals_woodbury_st64_kern
   double sq[NTN];  // z_eᵀ Σ_{f∈Q} z_f over this lane's columns (rows with Q signals)
 #pragma unroll
   for (int I = 0; I < NTN; ++I) sq[I] = 0.0;
-  constexpr int KEEP = wb64_keep<NTK, NTN>();
+  constexpr int KEEP = C::KEEP;
   double keep[KEEP > 0 ? KEEP : 1][NTN][4];
   {
     // a ring of KD + 1 chunk buffers: chunk s + KD is in flight while chunk s is consumed
     // (the loop unrolls fully, so every ring index is a compile-time constant)
-    constexpr int KD = wb64_kdepth<NTN>();
+    constexpr int KD = C::KD;
     double buf[KD + 1][NTN][4];
 #pragma unroll
     for (int s = 0; s < KD && s < NS; ++s) load_chunk(s, buf[s]);
@@ -857,12 +811,12 @@ __global__ __launch_bounds__(64, wb64_waves<NTN>()) void wals_woodbury_st64_kern
     // XD chunks in flight: the Gram's accumulators are dead here, so the x' pass can hold
     // a deeper ring than the K pass (each chunk costs little compute: its loads would
     // otherwise be waited for one after the other)
-    constexpr int XD = wb64_xdepth<NTN>();
+    constexpr int XD = C::XD;
     constexpr int KT = KEEP + KL;  // chunks kept on chip (registers, then LDS)
     constexpr int NG = NS - KT;    // chunks gathered again
     double buf[XD + 1][NTN][4];
 #pragma unroll
-    for (int q = 0; q < XD && q < NG; ++q) load_chunk_x(KT + q, buf[q]);
+    for (int q = 0; q < XD && q < NG; ++q) load_chunk(KT + q, buf[q]);
     double xbq = 0.0;
     auto xchunk = [&](int s, const double (&cur)[NTN][4]) {
       double sx[4];
@@ -904,7 +858,7 @@ __global__ __launch_bounds__(64, wb64_waves<NTN>()) void wals_woodbury_st64_kern
     }
 #pragma unroll
     for (int q = 0; q < NG; ++q) {
-      if (q + XD < NG) load_chunk_x(KT + q + XD, buf[(q + XD) % (XD + 1)]);
+      if (q + XD < NG) load_chunk(KT + q + XD, buf[(q + XD) % (XD + 1)]);
       xchunk(KT + q, buf[q % (XD + 1)]);
     }
     if (hasQ) xb = wave_sum(xbq);
@@ -928,356 +882,6 @@ __global__ __launch_bounds__(64, wb64_waves<NTN>()) void wals_woodbury_st64_kern
     o[5] = hw | ((uint64_t)xcc << 32);
     o[6] = (uint64_t)n;
     o[7] = (uint64_t)row;
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Whitening / unwhitening GEMMs with the inverse Cholesky factor Linv = L⁻¹ (lower, KP×KP).
-//   whiten:   Z[r] = Linv · Y[r]     (z = L⁻¹ y)            rows 0..n-1, 16 per wave
-//   unwhiten: X[r] = Linvᵀ · X'[r]   (x = L⁻ᵀ x') in place, rows from `order`; also
-//             rowloss[r] −= λ‖x‖².
-// One wave computes QMFX_WHITEN_RG 16-row × KP blocks with NT accumulator tiles each (two: each
-// L⁻¹ fragment serves two MFMAs; C3 fp64 382.9 → 381.5 ms/epoch); the zero upper
-// triangle of Linv is skipped.
-// ---------------------------------------------------------------------------------------
-// row groups of 16 per wave in the whitening GEMMs: each L⁻¹ operand fragment is loaded once
-// and used for RG groups' MFMAs
-#ifndef QMFX_WHITEN_RG
-#define QMFX_WHITEN_RG 2
-#endif
-template <typename T, int NT, bool UNWHITEN>
-__global__ __launch_bounds__(256) void whiten_kernel(const T* in, T* out, const int64_t* order,
-                                                     int64_t nrows, const T* __restrict__ Linv,
-                                                     double* rowloss, double lambda) {
-  using M = Mfma<T>;
-  using acc_t = typename M::acc_t;
-  constexpr int KP = 16 * NT;
-  constexpr int RG = QMFX_WHITEN_RG;
-  const int lane = threadIdx.x & 63;
-  const int cl = lane & 15;
-  const int kk = lane >> 4;
-  const int64_t rw = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (16 * RG);
-  if (rw >= nrows) return;
-  int64_t rowa[RG];
-#pragma unroll
-  for (int g = 0; g < RG; ++g) {
-    const int64_t r = rw + 16 * g + cl;
-    const int64_t ra = r < nrows ? r : nrows - 1;
-    rowa[g] = UNWHITEN ? order[ra] : ra;
-  }
-  acc_t acc[RG][NT];
-#pragma unroll
-  for (int g = 0; g < RG; ++g)
-#pragma unroll
-    for (int J = 0; J < NT; ++J) acc[g][J] = acc_t{0, 0, 0, 0};
-#pragma unroll
-  for (int s = 0; s < KP / 4; ++s) {
-    const int m = 4 * s + kk;
-    T av[RG];
-#pragma unroll
-    for (int g = 0; g < RG; ++g) av[g] = in[rowa[g] * KP + m];
-#pragma unroll
-    for (int J = 0; J < NT; ++J) {
-      const int j = 16 * J + cl;
-      if (UNWHITEN) {
-        // x_j = Σ_m x'_m Linv[m][j]: nonzero only for m ≥ j
-        if (4 * s + 3 >= 16 * J) {
-          const T bv = Linv[m * KP + j];
-#pragma unroll
-          for (int g = 0; g < RG; ++g) acc[g][J] = M::mma(av[g], bv, acc[g][J]);
-        }
-      } else {
-        // z_j = Σ_m Linv[j][m] y_m: nonzero only for m ≤ j
-        if (4 * s <= 16 * J + 15) {
-          const T bv = Linv[j * KP + m];
-#pragma unroll
-          for (int g = 0; g < RG; ++g) acc[g][J] = M::mma(av[g], bv, acc[g][J]);
-        }
-      }
-    }
-  }
-  // all reads of this wave's rows are done before any write (in-place unwhitening)
-#pragma unroll
-  for (int g = 0; g < RG; ++g) {
-    const int64_t r0 = rw + 16 * g;
-    T ss[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int64_t ro = r0 + M::crow(lane, r);
-      if (ro < nrows) {
-        const int64_t rowo = UNWHITEN ? order[ro] : ro;
-#pragma unroll
-        for (int J = 0; J < NT; ++J) {
-          out[rowo * KP + 16 * J + cl] = acc[g][J][r];
-          ss[r] += acc[g][J][r] * acc[g][J][r];
-        }
-      }
-    }
-    if (UNWHITEN) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const T tot = row16_sum(ss[r]);
-        const int64_t ro = r0 + M::crow(lane, r);
-        if (cl == 0 && ro < nrows) rowloss[order[ro]] -= lambda * (double)tot;
-      }
-    }
-  }
-}
-
-// The same GEMMs for KP ≤ 128 with L⁻¹ staged once per workgroup in LDS (round 6).  The
-// global-operand kernel above keeps its L⁻¹ fragments in the same VMEM queue as the row
-// gathers: of the ~18 loads a wave has in flight, two in seven are row bytes, so the rows
-// (the kernel's HBM traffic) arrive at ~3 TB/s (C3 fp64 unwhiten: 21.6 GB in 6.7 ms, PMC).
-// Here the B operand is an LDS read, every VMEM load in flight is a row load, and the grid
-// is persistent (one or two 512-thread workgroups per CU, each wave striding over 32-row
-// blocks), so L⁻¹ crosses the fabric once per workgroup instead of once per 32 rows.
-//   LDS layout: B[m][j] (= Linv[m][j] to unwhiten, Linv[j][m] to whiten) with a row pitch of
-//   KP + 16 elements (fp64: + 128 B), so the four K rows of one fragment read (lanes kk =
-//   0..3) fall on two disjoint halves of the banks.
-// ---------------------------------------------------------------------------------------
-#ifndef QMFX_WHITEN_LDS_D
-#define QMFX_WHITEN_LDS_D 4
-#endif
-#ifndef QMFX_WHITEN_LDS32
-#define QMFX_WHITEN_LDS32 0
-#endif
-#ifndef QMFX_WHITEN_LDS_RG
-#define QMFX_WHITEN_LDS_RG 2
-#endif
-template <typename T, int NT>
-struct WhitenLds {
-  static constexpr int KP = 16 * NT;
-  // row pitch KP + 16 elements: fp64 KP + 128 B (a fragment read's four K rows of 128 B on
-  // two bank halves), fp32 KP + 64 B (four 64-B rows on four bank quarters; 72 KB at k = 128,
-  // two workgroups per CU)
-  static constexpr int LDL = KP + 16;
-  static constexpr int BYTES = KP * LDL * (int)sizeof(T);
-  // fp64 only by default: at fp32 (C3) the kernel measured slower with one workgroup per CU
-  // (profiles/r06/ab_whiten_lds.txt); QMFX_WHITEN_LDS32 = 1 enables the two-per-CU form
-  static constexpr bool FITS =
-      (sizeof(T) == 8 || QMFX_WHITEN_LDS32) && NT <= 8 && BYTES <= 150 * 1024;
-  // workgroups per CU the LDS allows (at most 2: 16 waves)
-  static constexpr int PER_CU = BYTES <= 75 * 1024 ? 2 : 1;
-};
-template <typename T, int NT, bool UNWHITEN>
-__global__ __launch_bounds__(512) void whiten_lds_kernel(const T* in, T* out,
-                                                         const int64_t* order, int64_t nrows,
-                                                         const T* __restrict__ Linv,
-                                                         double* rowloss, double lambda) {
-  using M = Mfma<T>;
-  using acc_t = typename M::acc_t;
-  using W = WhitenLds<T, NT>;
-  constexpr int KP = W::KP;
-  constexpr int LDL = W::LDL;
-  constexpr int RG = QMFX_WHITEN_LDS_RG;
-  __shared__ __attribute__((aligned(16))) T B[KP * LDL];
-  for (int i = threadIdx.x; i < KP * KP; i += 512) {
-    const int r = i / KP, c = i % KP;
-    const T v = Linv[i];
-    if (UNWHITEN)
-      B[r * LDL + c] = v;
-    else
-      B[c * LDL + r] = v;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int cl = lane & 15;
-  const int kk = lane >> 4;
-  const int64_t stride = (int64_t)gridDim.x * 8 * (16 * RG);
-  for (int64_t rw = ((int64_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * (16 * RG); rw < nrows;
-       rw += stride) {
-    int64_t rowa[RG];
-#pragma unroll
-    for (int g = 0; g < RG; ++g) {
-      const int64_t r = rw + 16 * g + cl;
-      const int64_t ra = r < nrows ? r : nrows - 1;
-      rowa[g] = UNWHITEN ? order[ra] : ra;
-    }
-    acc_t acc[RG][NT];
-#pragma unroll
-    for (int g = 0; g < RG; ++g)
-#pragma unroll
-      for (int J = 0; J < NT; ++J) acc[g][J] = acc_t{0, 0, 0, 0};
-    // the row values of step s + D are in flight while step s's MFMAs run (each step is its
-    // own scheduling region, or the compiler hoists every step's LDS reads and spills)
-    constexpr int NS = KP / 4;
-    constexpr int D = QMFX_WHITEN_LDS_D < NS ? QMFX_WHITEN_LDS_D : NS;
-    T ring[D][RG];
-#pragma unroll
-    for (int s = 0; s < D; ++s)
-#pragma unroll
-      for (int g = 0; g < RG; ++g) ring[s][g] = in[rowa[g] * KP + 4 * s + kk];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const int m = 4 * s + kk;
-      T av[RG];
-#pragma unroll
-      for (int g = 0; g < RG; ++g) av[g] = ring[s % D][g];
-      if (s + D < NS) {
-#pragma unroll
-        for (int g = 0; g < RG; ++g) ring[s % D][g] = in[rowa[g] * KP + 4 * (s + D) + kk];
-      }
-#pragma unroll
-      for (int J = 0; J < NT; ++J) {
-        // unwhiten: x_j = Σ_{m ≥ j} Linv[m][j] x'_m; whiten: z_j = Σ_{m ≤ j} Linv[j][m] y_m
-        const bool live = UNWHITEN ? (4 * s + 3 >= 16 * J) : (4 * s <= 16 * J + 15);
-        if (live) {
-          const T bv = B[m * LDL + 16 * J + cl];
-#pragma unroll
-          for (int g = 0; g < RG; ++g) acc[g][J] = M::mma(av[g], bv, acc[g][J]);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // all reads of this block's rows are done before any write (in-place unwhitening)
-#pragma unroll
-    for (int g = 0; g < RG; ++g) {
-      const int64_t r0 = rw + 16 * g;
-      T ss[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int64_t ro = r0 + M::crow(lane, r);
-        if (ro < nrows) {
-          const int64_t rowo = UNWHITEN ? order[ro] : ro;
-#pragma unroll
-          for (int J = 0; J < NT; ++J) {
-            out[rowo * KP + 16 * J + cl] = acc[g][J][r];
-            ss[r] += acc[g][J][r] * acc[g][J][r];
-          }
-        }
-      }
-      if (UNWHITEN) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const T tot = row16_sum(ss[r]);
-          const int64_t ro = r0 + M::crow(lane, r);
-          if (cl == 0 && ro < nrows) rowloss[order[ro]] -= lambda * (double)tot;
-        }
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// M = G + λI (padding: 1) → L (Cholesky, fp64, in LDS) → Linv = L⁻¹ written in T.
-// One 256-thread workgroup; run once per half when whitened rows exist.
-// ---------------------------------------------------------------------------------------
-template <typename T, int NT>
-__global__ __launch_bounds__(256) void chol_inv_kernel(const T* G, int k, double lambda,
-                                                       T* Linv, int32_t* status) {
-  constexpr int KP = 16 * NT;
-  constexpr int LD = KP + 1;
-  __shared__ double A[KP * LD];
-  __shared__ double dinv[KP];
-  const int tid = threadIdx.x;
-  for (int idx = tid; idx < KP * KP; idx += 256) {
-    const int i = idx / KP, j = idx % KP;
-    double v = (double)G[idx];
-    if (i == j) v += i < k ? lambda : 1.0;
-    A[i * LD + j] = v;
-  }
-  __syncthreads();
-  for (int j = 0; j < KP; ++j) {
-    if (tid == 0) {
-      const double d = A[j * LD + j];
-      if (!(d > 0.0)) *status = 1;
-      const double l = sqrt(d > 0.0 ? d : 1.0);
-      A[j * LD + j] = l;
-      dinv[j] = 1.0 / l;
-    }
-    __syncthreads();
-    for (int i = j + 1 + tid; i < KP; i += 256) A[i * LD + j] *= dinv[j];
-    __syncthreads();
-    const int m = KP - j - 1;  // trailing size
-    for (int idx = tid; idx < m * m; idx += 256) {
-      const int ii = j + 1 + idx / m, mm = j + 1 + idx % m;
-      if (mm <= ii) A[ii * LD + mm] -= A[ii * LD + j] * A[mm * LD + j];
-    }
-    __syncthreads();
-  }
-  // Linv column c (thread c): Linv[c][c] = 1/L[c][c];
-  // Linv[i][c] = −(Σ_{m=c}^{i−1} L[i][m] Linv[m][c]) / L[i][i], kept in A's upper triangle
-  // at A[c][i] (row c is private to thread c)
-  if (tid < KP) {
-    const int c = tid;
-    for (int i = c + 1; i < KP; ++i) {
-      double s = A[i * LD + c] * dinv[c];
-      for (int m = c + 1; m < i; ++m) s += A[i * LD + m] * A[c * LD + m];
-      A[c * LD + i] = -s * dinv[i];
-    }
-  }
-  __syncthreads();
-  for (int idx = tid; idx < KP * KP; idx += 256) {
-    const int i = idx / KP, c = idx % KP;
-    double v = 0.0;
-    if (i == c) v = dinv[c];
-    else if (i > c) v = A[c * LD + i];
-    Linv[idx] = (T)v;
-  }
-}
-
-// The same factorization for KP > 128 (the fp64 matrix exceeds LDS): one 1024-thread
-// workgroup on a global fp64 scratch of KP·(KP+1) doubles (L2-resident; __syncthreads
-// orders the block's global accesses).  Once per half; ≈ms at KP = 256.
-template <typename T, int NT>
-__global__ __launch_bounds__(1024) void chol_inv_global_kernel(const T* G, int k, double lambda,
-                                                               T* Linv, int32_t* status,
-                                                               double* A) {
-  constexpr int KP = 16 * NT;
-  constexpr int LD = KP + 1;
-  static_assert(4 * KP <= 1024, "the inverse gives each of the KP columns 4 of the 1024 threads");
-  __shared__ double dinv[KP];
-  const int tid = threadIdx.x;
-  for (int idx = tid; idx < KP * KP; idx += 1024) {
-    const int i = idx / KP, j = idx % KP;
-    double v = (double)G[idx];
-    if (i == j) v += i < k ? lambda : 1.0;
-    A[i * LD + j] = v;
-  }
-  __syncthreads();
-  for (int j = 0; j < KP; ++j) {
-    if (tid == 0) {
-      const double d = A[j * LD + j];
-      if (!(d > 0.0)) *status = 1;
-      const double l = sqrt(d > 0.0 ? d : 1.0);
-      A[j * LD + j] = l;
-      dinv[j] = 1.0 / l;
-    }
-    __syncthreads();
-    for (int i = j + 1 + tid; i < KP; i += 1024) A[i * LD + j] *= dinv[j];
-    __syncthreads();
-    const int m = KP - j - 1;
-    for (int idx = tid; idx < m * m; idx += 1024) {
-      const int ii = j + 1 + idx / m, mm = j + 1 + idx % m;
-      if (mm <= ii) A[ii * LD + mm] -= A[ii * LD + j] * A[mm * LD + j];
-    }
-    __syncthreads();
-  }
-  // L⁻¹ column c by forward substitution on four threads (lanes 4c .. 4c + 3 of one wave):
-  // thread q sums the terms mm ≡ q (mod 4), two shuffles combine them, and entry i is stored
-  // by the thread that will read it again (q = i mod 4), so each thread only re-reads its own
-  // writes.  One thread per column left the k = 256 launch at 6.2 ms, the column chains
-  // (up to 32K dependent-address FMAs) being the whole of it.
-  {
-    const int c = tid >> 2, q = tid & 3;
-    if (c < KP) {
-      for (int i = c + 1; i < KP; ++i) {
-        double sm = q == 0 ? A[i * LD + c] * dinv[c] : 0.0;
-        int mm = c + 1 + ((q - (c + 1)) & 3);
-        for (; mm < i; mm += 4) sm += A[i * LD + mm] * A[c * LD + mm];
-        sm += __shfl_xor(sm, 1, 64);
-        sm += __shfl_xor(sm, 2, 64);
-        if ((i & 3) == q) A[c * LD + i] = -sm * dinv[i];
-      }
-    }
-  }
-  __syncthreads();
-  for (int idx = tid; idx < KP * KP; idx += 1024) {
-    const int i = idx / KP, c = idx % KP;
-    double v = 0.0;
-    if (i == c) v = dinv[c];
-    else if (i > c) v = A[c * LD + i];
-    Linv[idx] = (T)v;
   }
 }
 
@@ -1331,93 +935,13 @@ static hipError_t launch_woodbury_f64_ntk(const SolveArgs<double>& a, int ntn, h
   });
 }
 
-template <typename T, int NT>
-static hipError_t launch_whiten_nt(const T* in, T* out, const int64_t* order, int64_t nrows,
-                                   const T* Linv, double* rowloss, double lambda, bool unwhiten,
-                                   int cus, hipStream_t s) {
-  if (nrows <= 0) return hipSuccess;
-  if constexpr (WhitenLds<T, NT>::FITS) {
-    if (cus <= 0) return hipErrorInvalidValue;
-    const int64_t need = (nrows + 8 * 16 * QMFX_WHITEN_LDS_RG - 1) / (8 * 16 * QMFX_WHITEN_LDS_RG);
-    int64_t cap = (int64_t)cus * WhitenLds<T, NT>::PER_CU;
-    // test hook (read per launch): fewer workgroups, so that every wave strides over several
-    // 32-row blocks at test sizes
-    if (const char* g = std::getenv("QMFX_WHITEN_GRID")) {
-      const long v = std::strtol(g, nullptr, 10);
-      if (v > 0 && v < cap) cap = v;
-    }
-    const unsigned grid = (unsigned)(need < cap ? need : cap);
-    if (unwhiten)
-      hipLaunchKernelGGL((whiten_lds_kernel<T, NT, true>), dim3(grid), dim3(512), 0, s, in, out,
-                         order, nrows, Linv, rowloss, lambda);
-    else
-      hipLaunchKernelGGL((whiten_lds_kernel<T, NT, false>), dim3(grid), dim3(512), 0, s, in,
-                         out, order, nrows, Linv, rowloss, lambda);
-  } else {
-    const unsigned blocks = (unsigned)((nrows + 64 * QMFX_WHITEN_RG - 1) / (64 * QMFX_WHITEN_RG));
-    if (unwhiten)
-      hipLaunchKernelGGL((whiten_kernel<T, NT, true>), dim3(blocks), dim3(256), 0, s, in, out,
-                         order, nrows, Linv, rowloss, lambda);
-    else
-      hipLaunchKernelGGL((whiten_kernel<T, NT, false>), dim3(blocks), dim3(256), 0, s, in, out,
-                         order, nrows, Linv, rowloss, lambda);
-  }
-  return hipGetLastError();
-}
-
-template <typename T, int NT>
-static hipError_t launch_chol_inv_nt(const T* G, int k, double lambda, T* Linv, int32_t* status,
-                                     double* scratch, hipStream_t s) {
-  if constexpr (NT > 8) {
-    if (!scratch) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((chol_inv_global_kernel<T, NT>), dim3(1), dim3(1024), 0, s, G, k, lambda,
-                       Linv, status, scratch);
-    return hipGetLastError();
-  } else {
-    (void)scratch;
-    hipLaunchKernelGGL((chol_inv_kernel<T, NT>), dim3(1), dim3(256), 0, s, G, k, lambda, Linv,
-                       status);
-    return hipGetLastError();
-  }
-}
-
 hipError_t launch_wals_woodbury(const SolveArgs<float>& a, int nt, int ntn, hipStream_t s) {
-#define CALL(N) launch_woodbury_f32_ntk<N>(a, ntn, s)
-  QMFX_NT_SWITCH_W(nt, CALL)
-#undef CALL
+  return dispatch_nt_w(
+      nt, [&](auto N) { return launch_woodbury_f32_ntk<decltype(N)::value>(a, ntn, s); });
 }
 hipError_t launch_wals_woodbury(const SolveArgs<double>& a, int nt, int ntn, hipStream_t s) {
-#define CALL(N) launch_woodbury_f64_ntk<N>(a, ntn, s)
-  QMFX_NT_SWITCH_W(nt, CALL)
-#undef CALL
-}
-hipError_t launch_whiten(const float* in, float* out, const int64_t* order, int64_t nrows,
-                         int nt, const float* Linv, double* rowloss, double lambda,
-                         bool unwhiten, int cus, hipStream_t s) {
-#define CALL(N) \
-  launch_whiten_nt<float, N>(in, out, order, nrows, Linv, rowloss, lambda, unwhiten, cus, s)
-  QMFX_NT_SWITCH_W(nt, CALL)
-#undef CALL
-}
-hipError_t launch_whiten(const double* in, double* out, const int64_t* order, int64_t nrows,
-                         int nt, const double* Linv, double* rowloss, double lambda,
-                         bool unwhiten, int cus, hipStream_t s) {
-#define CALL(N) \
-  launch_whiten_nt<double, N>(in, out, order, nrows, Linv, rowloss, lambda, unwhiten, cus, s)
-  QMFX_NT_SWITCH_W(nt, CALL)
-#undef CALL
-}
-hipError_t launch_chol_inv(const float* G, int nt, int k, double lambda, float* Linv,
-                           int32_t* status, double* scratch, hipStream_t s) {
-#define CALL(N) launch_chol_inv_nt<float, N>(G, k, lambda, Linv, status, scratch, s)
-  QMFX_NT_SWITCH_W(nt, CALL)
-#undef CALL
-}
-hipError_t launch_chol_inv(const double* G, int nt, int k, double lambda, double* Linv,
-                           int32_t* status, double* scratch, hipStream_t s) {
-#define CALL(N) launch_chol_inv_nt<double, N>(G, k, lambda, Linv, status, scratch, s)
-  QMFX_NT_SWITCH_W(nt, CALL)
-#undef CALL
+  return dispatch_nt_w(
+      nt, [&](auto N) { return launch_woodbury_f64_ntk<decltype(N)::value>(a, ntn, s); });
 }
 #endif  // QMFX_KERNELS_ONLY
 

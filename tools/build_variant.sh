@@ -1,10 +1,12 @@
 #!/bin/bash
-# Timing experiments: build qmf_amd/_build/var_<name>.so = libqmfx with one source compiled
-# under extra -D flags (csrc/wals.hip by default; SRC=woodbury tools/build_variant.sh ..., or
-# SRCPATH=<path to a .hip> for an experimental copy, e.g. under tools/exp/).  The variant links a
-# tag object, so qmfx_build_variant() returns its flags and bench.py refuses to report it as
-# the product (unless --allow-variant, which marks the line).
-# usage: tools/build_variant.sh name "-DFOO=1 -DBAR=2"
+# Timing experiments: build qmf_amd/_build/var_<name>.so = libqmfx with one source replaced by
+# an edited copy of it (SRCPATH=<path to a .hip>, e.g. under tools/exp/; the kernels'
+# configuration is constexpr values in the sources, not -D switches, so a variant edits a copy).
+# SRC=<unit> recompiles the tree's own csrc/<unit>.hip (csrc/wals.hip by default), for extra
+# compiler flags such as -mllvm options.  The variant links a tag object, so
+# qmfx_build_variant() returns its source and flags and bench.py refuses to report it as the
+# product (unless --allow-variant, which marks the line).
+# usage: SRCPATH=tools/exp/woodbury.hip tools/build_variant.sh name ["extra compiler flags"]
 set -e
 cd "$(dirname "$0")/../qmf_amd"
 B=_build

@@ -1,7 +1,10 @@
 #!/bin/bash
-# Timing experiments: qmf_amd/_build/var_<name>.so = libqmfx with the listed sources rebuilt
-# under extra -D flags (compiled in parallel; per-file Makefile flags kept).
-# usage: tools/build_variant_multi.sh name "-DFOO=1" woodbury wals_direct_f64 ...
+# Timing experiments: qmf_amd/_build/var_<name>.so = libqmfx with the listed sources replaced
+# by edited copies of them under tools/exp/ (a unit with no csrc/<unit>.hip of that name is
+# taken from there; the kernels' configuration is constexpr values in the sources, not -D
+# switches), compiled in parallel with the per-file Makefile flags kept.  A unit that csrc/ has
+# is rebuilt from the tree, for extra compiler flags; the resource usage lands in *.ra.
+# usage: tools/build_variant_multi.sh name "extra compiler flags" woodbury_exp wals_direct_f64 ...
 set -e
 cd "$(dirname "$0")/../qmf_amd"
 B=_build
