@@ -188,6 +188,37 @@ int qmfx_recommend(qmfx_ctx* ctx, int64_t nusers, const int64_t* users, int topn
                    int use_biases, int64_t* items /*nusers·topn*/, double* scores /*nusers·topn*/,
                    int32_t* counts /*nusers*/);
 
+/* ---- similar rows: top-N neighbours in factor space ----------------------------------------
+ * For each of the nq query rows of `side` (row idx; any order, repeats allowed) the device
+ * scores every row of the same side against the query row and selects the best eligible ones,
+ * without a score matrix.  All arithmetic is double, on the factor values the device holds (an
+ * fp32 context's values widened); item biases are never used.
+ *   dot(a, b)     s = 0.0, then s = s + a_f * b_f for f = 0..k-1, one rounded multiply and one
+ *                 rounded add each, never fused: qmfx_recommend's score without a bias.
+ *   norm(a)       sqrt(dot(a, a)), the sqrt correctly rounded.  qmfx_factor_norms returns
+ *                 these values for every row of `side` (n_side doubles).
+ *   cosine(a, b)  den = norm(a) * norm(b) (one rounded multiply); dot(a, b) / den (one
+ *                 correctly rounded divide) when den > 0, else 0.0: a zero row, or a product
+ *                 that underflows to 0, scores 0.0, never NaN.
+ * metric selects the score: QMFX_SIM_DOT or QMFX_SIM_COSINE.  The order is qmfx_recommend's:
+ * row x ranks before row y when score_x > score_y, or score_x == score_y and x < y; the
+ * comparison is numeric (-0.0 equals +0.0).  NaN or infinite factor values are out of contract.
+ * Every row of the side is eligible, except, with exclude_self != 0, the row whose index is
+ * the query's: exclusion is by index, so an exact duplicate of the query row stays eligible.
+ * Query t's answer is the first counts[t] = min(topn, eligible) rows in that order:
+ * neighbours[t*topn + r] (row idx) and scores[t*topn + r] for rank r; the unused tail carries
+ * -1 and 0.0.  topn is 1..QMFX_REC_MAX_N.
+ * Fails (-1, with a message) on: side not 0 or 1, topn out of range, an unknown metric, a row
+ * index out of range, no factors, nfactors > 256 (qmfx_similar only).  A context sharded by
+ * qmfx_dist_init* answers for any row on any rank, the factors being full replicas.  nq == 0
+ * succeeds and touches nothing.  The norms are computed by every call, never cached. */
+#define QMFX_SIM_DOT 0
+#define QMFX_SIM_COSINE 1
+int qmfx_factor_norms(qmfx_ctx* ctx, int side, double* norms /*n_side*/);
+int qmfx_similar(qmfx_ctx* ctx, int side, int64_t nq, const int64_t* rows, int topn, int metric,
+                 int exclude_self, int64_t* neighbours /*nq·topn*/, double* scores /*nq·topn*/,
+                 int32_t* counts /*nq*/);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) -------------------------------------- */
 int qmfx_rccl_unique_id(uint8_t* id128);
 /* Joins the RCCL communicator (id128 from rank 0's qmfx_rccl_unique_id), takes this rank's
@@ -218,7 +249,8 @@ int qmfx_dist_plan(const int64_t* rowptr, int64_t nrows, int world, int npieces,
 
 /* ---- measurement -------------------------------------------------------------------------- */
 /* HIP-event time of the row-solve kernel launches (on the context stream) since reset; the
- * kernels of qmfx_bpr_epoch and qmfx_recommend calls are counted here too. */
+ * kernels of qmfx_bpr_epoch, qmfx_recommend and qmfx_similar calls are counted here too (one
+ * unit of a similar call is 2k flop per (query, row) pair). */
 int qmfx_solve_kernel_stats(qmfx_ctx* ctx, double* total_ms, int64_t* launches,
                             double* flops, double* bytes);
 /* Per kernel class since reset: 0 = direct row kernel, 1 = whitened row kernels (row solve

@@ -8,7 +8,7 @@ GPU is present the calls fail loudly.
 """
 from ._abi import (  # noqa: F401
     LIB_PATH, QmfxError, Context, build, device_count, dist_init_all, dist_plan, lib, partition_rows, rccl_unique_id, selftest_mfma,
-    version, wals_half_multi,
+    version, wals_half_multi, QMFX_SIM_DOT, QMFX_SIM_COSINE,
 )
 
 USERS = 0

@@ -57,6 +57,8 @@ SIGNATURES = {
     "qmfx_eval_set_labels": [vp, c_i64, P_i64, P_i64, P_i64, P_f64],
     "qmfx_eval_ranks": [vp, c_int, P_f64, P_i64, P_f64],
     "qmfx_recommend": [vp, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64, P_i32],
+    "qmfx_factor_norms": [vp, c_int, P_f64],
+    "qmfx_similar": [vp, c_int, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64, P_i32],
     "qmfx_rccl_unique_id": [P_u8],
     "qmfx_dist_init": [vp, c_int, c_int, P_u8],
     "qmfx_partition_rows": [P_i64, c_i64, c_int, c_int, P_i64, P_i64],
@@ -72,6 +74,9 @@ SIGNATURES = {
     "qmfx_build_variant": [],
     "qmfx_selftest_mfma": [c_int, c_int, P_f64, P_f64, P_f64],
 }
+QMFX_SIM_DOT = 0
+QMFX_SIM_COSINE = 1
+
 _RESTYPE = {"qmfx_last_error": ctypes.c_char_p, "qmfx_build_variant": ctypes.c_char_p}
 
 _lib = None
@@ -387,6 +392,28 @@ class Context:
                                     int(use_biases), _p(items, P_i64), _p(scores, P_f64),
                                     _p(counts, P_i32)))
         return items, scores, counts
+
+    # ---- similar rows
+    def factor_norms(self, side):
+        """The norm of every row of `side`: sqrt of the sequential, unfused sum of squares
+        (include/qmfx.h qmfx_factor_norms)."""
+        out = np.empty(self._n(side), np.float64)
+        _check(lib().qmfx_factor_norms(self.h, int(side), _p(out, P_f64)))
+        return out
+
+    def similar(self, side, rows, topn, metric=QMFX_SIM_COSINE, exclude_self=True):
+        """(neighbours[n, topn], scores[n, topn], counts[n]) for the row indices `rows` of
+        `side`, ranked among the rows of the same side: see include/qmfx.h qmfx_similar
+        (metric: QMFX_SIM_DOT or QMFX_SIM_COSINE)."""
+        rows = np.ascontiguousarray(rows, np.int64)
+        n, w = len(rows), max(int(topn), 0)
+        neighbours = np.empty((n, w), np.int64)
+        scores = np.empty((n, w), np.float64)
+        counts = np.empty(n, np.int32)
+        _check(lib().qmfx_similar(self.h, int(side), n, _p(rows, P_i64), int(topn), int(metric),
+                                  int(bool(exclude_self)), _p(neighbours, P_i64),
+                                  _p(scores, P_f64), _p(counts, P_i32)))
+        return neighbours, scores, counts
 
     # ---- dist / stats
     def dist_init(self, rank, world, uid):

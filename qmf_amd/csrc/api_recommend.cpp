@@ -3,20 +3,6 @@
 
 using namespace qmfx;
 
-namespace {
-
-// scratch grown on demand: keeps the buffer when it already holds `bytes`
-template <typename T>
-int grow(DevPtr<T>& p, size_t& cap, size_t bytes) {
-  if (p && cap >= bytes) return 0;
-  cap = 0;
-  HIPCHK(dev_alloc(p, bytes));
-  cap = bytes;
-  return 0;
-}
-
-}  // namespace
-
 extern "C" {
 
 int qmfx_recommend(qmfx_ctx* c, int64_t nusers, const int64_t* users, int topn, int exclude,

@@ -162,12 +162,15 @@ struct qmfx_ctx {
   qmfx::DevPtr<double> ev_lscore, ev_pscore;
   qmfx::DevPtr<unsigned long long> ev_above;
   qmfx::DevPtr<double> ev_sq, ev_udbl;
-  // top-N recommendations (qmfx_recommend): scratch grown on demand (rc_cap: bytes held, in
+  // top-N recommendations (qmfx_recommend; qmfx_similar shares it): scratch grown on demand (rc_cap: bytes held, in
   // the members' order)
   qmfx::DevPtr<int64_t> rc_users, rc_items;
   qmfx::DevPtr<double> rc_udbl, rc_pscore, rc_scores;
   qmfx::DevPtr<int32_t> rc_pitem, rc_pcnt, rc_counts;
   size_t rc_cap[8] = {};
+  // similar rows (qmfx_similar, qmfx_factor_norms): one side's row norms, written by every call
+  qmfx::DevPtr<double> sim_norms;
+  size_t sim_cap = 0;
   uint64_t bpr_epochs = 0;
   // QMFX_FAULT_COMM_RANK=<rank>[:<after>] (tests), read once at create: that rank's piece
   // broadcasts fail as if RCCL had failed once <after> of them have succeeded (-1: none)
@@ -268,6 +271,16 @@ inline hipError_t copy_out(qmfx_ctx* c, double* dst, const void* src, size_t n) 
   const hipError_t e = scopy(c, v.data(), src, n * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess) std::copy(v.begin(), v.end(), dst);
   return e;
+}
+
+// scratch grown on demand: keeps the buffer when it already holds `bytes`
+template <typename T>
+int grow(DevPtr<T>& p, size_t& cap, size_t bytes) {
+  if (p && cap >= bytes) return 0;
+  cap = 0;
+  HIPCHK(dev_alloc(p, bytes));
+  cap = bytes;
+  return 0;
 }
 
 // col/val as the kernels index them: with the global rowptr (see SideBuf::shard_off)

@@ -306,4 +306,22 @@ struct RecArgs {
 hipError_t launch_recommend(const RecArgs<float>& a, hipStream_t s);
 hipError_t launch_recommend(const RecArgs<double>& a, hipStream_t s);
 
+// Top-N neighbours of a side's rows among the rows of the same side (recommend.hip): the
+// selection of RecArgs with U = I = the side's factors, users = the query rows, nitems = the
+// side's rows, no bias and no seen lists.
+template <typename T>
+struct SimArgs : RecArgs<T> {
+  const double* norms;       // [nitems] row norms (launch_factor_norms); cosine only
+  int cosine;                // 0: dot, else dot / (norm · norm)
+  int exclude_self;          // the query row itself is not eligible
+};
+hipError_t launch_similar(const SimArgs<float>& a, hipStream_t s);
+hipError_t launch_similar(const SimArgs<double>& a, hipStream_t s);
+// norms[r] = sqrt(Σ_f F[r][f]²) in double, the sum in factor order with one rounded multiply
+// and one rounded add per factor
+hipError_t launch_factor_norms(const float* F, int64_t n, int k, int kp, double* norms,
+                               hipStream_t s);
+hipError_t launch_factor_norms(const double* F, int64_t n, int k, int kp, double* norms,
+                               hipStream_t s);
+
 }  // namespace qmfx

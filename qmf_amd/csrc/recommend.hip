@@ -28,9 +28,17 @@
 // window, wave-uniform bounds) are held one per lane and each lane binary-searches them for
 // its item with lane shuffles.  Bound: fp64 VALU (2 instructions per multiply-add).
 //
+// Similar rows (qmfx_similar) are the same selection with the query rows taken from the matrix
+// they are ranked against: rec_select_kernel's similarity modes (compile time; the recommend
+// instantiation is the kernel it was) rank a side's rows by dot product, or by cosine with the
+// row norms of rec_norms_kernel (sqrt of the same unfused sum), and can leave the query's own
+// row out by index.  Norms are recomputed per call: O(n·k), about one query's work.
+//
 // LDS of rec_select_kernel (dynamic, one configuration): 32 lists × 256 × 12 B = 96 KiB, the
 // per-user state 1,280 B, the item tile 64 × 66 × sizeof(T): 133,376 B (fp64) / 116,480 B
 // (fp32), one workgroup per CU.
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 
@@ -68,7 +76,21 @@ __device__ __forceinline__ double mul_add_rn(double s, double a, double b) {
   const double p = a * b;
   return s + p;
 }
+// dot / (na · nb): one rounded multiply, then one correctly rounded divide; 0.0 when the
+// product of the norms is not positive (a zero row, or a product that underflows)
+__device__ __forceinline__ double cosine_rn(double dot, double na, double nb) {
+  const double den = na * nb;
+  return den > 0.0 ? dot / den : 0.0;
+}
 #pragma clang fp contract(on)
+
+// what rec_select_kernel ranks: a user's items by score (qmfx_recommend), or a row's
+// neighbours on its own side by dot product or cosine (qmfx_similar)
+// (plain ints: an unnamed enum in the kernel's signature is mangled differently by the host
+// and the device compilation, and the launch then finds no kernel)
+constexpr int SEL_RECOMMEND = 0, SEL_SIM_DOT = 1, SEL_SIM_COSINE = 2;
+template <typename T, int Mode>
+using SelArgs = std::conditional_t<Mode == SEL_RECOMMEND, RecArgs<T>, SimArgs<T>>;
 
 // (score a, item a) ranks before (score b, item b)
 __device__ __forceinline__ bool rec_before(double sa, int32_t ia, double sb, int32_t ib) {
@@ -154,8 +176,31 @@ __global__ __launch_bounds__(256) void rec_users_kernel(RecArgs<T> a) {
     o[f * RC_UW] = t < a.nreq ? (double)u[f] : 0.0;
 }
 
+// One row's norm per thread: the squares summed in factor order, as mul_add_rn sums a score.
 template <typename T>
-__global__ __launch_bounds__(256) void rec_select_kernel(RecArgs<T> a) {
+__global__ __launch_bounds__(256) void rec_norms_kernel(const T* __restrict__ F, int64_t n, int k,
+                                                        int kp, double* __restrict__ norms) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const T* row = F + r * kp;
+  double s = 0.0;
+  // eight loads in flight; kp is a multiple of 16, so they stay inside the row
+  for (int f0 = 0; f0 < k; f0 += 8) {
+    T v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = row[f0 + j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (f0 + j < k) s = mul_add_rn(s, (double)v[j], (double)v[j]);
+  }
+  norms[r] = __builtin_sqrt(s);  // correctly rounded (no fast-math in this build)
+}
+
+// Mode SEL_RECOMMEND is qmfx_recommend's kernel.  The similarity modes (a.U == a.I, no bias, no
+// seen lists) differ after the dot accumulation only: cosine divides by the two rows' norms,
+// and with exclude_self the lane whose row is the query's own row does not propose.
+template <typename T, int Mode>
+__global__ __launch_bounds__(256) void rec_select_kernel(SelArgs<T, Mode> a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* const cand_s = (double*)smem;
   int32_t* const cand_i = (int32_t*)(smem + RC_OFF_CI);
@@ -176,6 +221,7 @@ __global__ __launch_bounds__(256) void rec_select_kernel(RecArgs<T> a) {
   // wave-uniform rows, read through the constant address space so they become scalar loads
   typedef const __attribute__((address_space(4))) double* cdptr;
   const cdptr ud = (cdptr)(a.udbl + (tw - a.t_base) * a.k);  // [f][8] for this wave's users
+  constexpr bool kSim = Mode != SEL_RECOMMEND;
 
   // The state of this wave's users (only this wave touches it, so no barrier orders it):
   // an empty list without threshold, and the seen-list cursor at the chunk's first item.
@@ -183,7 +229,7 @@ __global__ __launch_bounds__(256) void rec_select_kernel(RecArgs<T> a) {
     const int u = w * RC_UW + lane;
     const int64_t t = tw + lane;
     int64_t lo = 0, end = 0;
-    if (a.seen_ptr && t < a.nreq) {
+    if (!kSim && a.seen_ptr && t < a.nreq) {
       const int64_t row = a.users[t];
       lo = a.seen_ptr[row];
       end = a.seen_ptr[row + 1];
@@ -209,7 +255,7 @@ __global__ __launch_bounds__(256) void rec_select_kernel(RecArgs<T> a) {
     const bool valid = item < i1;
     const int32_t item32 = (int32_t)(uint32_t)item;
     double acc[RC_UW];
-    const double b0 = (a.bias && valid) ? (double)a.bias[item] : 0.0;
+    const double b0 = (!kSim && a.bias && valid) ? (double)a.bias[item] : 0.0;
 #pragma unroll
     for (int g = 0; g < RC_UW; ++g) acc[g] = b0;
     for (int f0 = 0; f0 < a.k; f0 += RC_KC) {
@@ -241,7 +287,7 @@ __global__ __launch_bounds__(256) void rec_select_kernel(RecArgs<T> a) {
 
     // which of the tile's items each user has seen: the list entries below the tile's end
     // (all ≥ ib: the cursor has passed everything below), 64 at a time, one per lane
-    if (a.seen_ptr) {
+    if (!kSim && a.seen_ptr) {
       const int64_t iend = ib + RC_TI < i1 ? ib + RC_TI : i1;
       for (int g = 0; g < RC_UW; ++g) {
         const int u = w * RC_UW + g;
@@ -265,7 +311,10 @@ __global__ __launch_bounds__(256) void rec_select_kernel(RecArgs<T> a) {
       }
     }
 
-    // proposals: valid, unseen and ranking before the user's threshold
+    // proposals: valid, unseen (similarity: not the query's own row) and ranking before the
+    // user's threshold
+    double cn = 0.0;  // this lane's row norm
+    if constexpr (Mode == SEL_SIM_COSINE) cn = valid ? a.norms[item] : 0.0;
 #pragma unroll
     for (int g = 0; g < RC_UW; ++g) {
       if (tw + g >= a.nreq) break;  // uniform over the wave
@@ -273,7 +322,16 @@ __global__ __launch_bounds__(256) void rec_select_kernel(RecArgs<T> a) {
       const int cnt = uniform(st_cnt[u]);
       const int32_t thi = st_thi[u];
       const double ths = st_thr[u];
-      const bool seen = (st_seen[u] >> lane) & 1ull;
+      int64_t self = -1;  // similarity: the query's own row when that is excluded
+      if constexpr (kSim) {
+        // the query's row index and norm: wave-uniform, through the constant address space
+        typedef const __attribute__((address_space(4))) int64_t* cqptr;
+        const int64_t q = ((cqptr)a.users)[tw + g];
+        if constexpr (Mode == SEL_SIM_COSINE)  // in place: the proposal below is one text
+          acc[g] = cosine_rn(acc[g], ((cdptr)a.norms)[q], cn);
+        if (a.exclude_self) self = q;
+      }
+      const bool seen = kSim ? item == self : (bool)((st_seen[u] >> lane) & 1ull);
       const bool propose = valid && !seen && (thi < 0 || rec_before(acc[g], item32, ths, thi));
       const RecList L{cand_s + u * RC_CAP, cand_i + u * RC_CAP};
       const int n = rec_append(L, cnt, propose, acc[g], item32);
@@ -372,13 +430,13 @@ __global__ __launch_bounds__(64) void rec_merge_kernel(RecMergeArgs a) {
   if (lane == 0) a.counts[t] = cnt;
 }
 
-template <typename T>
-hipError_t recommend(const RecArgs<T>& a0, hipStream_t s) {
+template <typename T, int Mode>
+hipError_t select(const SelArgs<T, Mode>& a0, hipStream_t s) {
   if (a0.k > RC_KMAX || a0.topn < 1 || a0.topn > kRecMaxN) return hipErrorInvalidValue;
   if (a0.nreq == 0) return hipSuccess;
-  RecArgs<T> a = a0;
+  SelArgs<T, Mode> a = a0;
   // above 64 KiB of LDS: dynamic shared memory with the function's limit raised
-  hipError_t e = hipFuncSetAttribute((const void*)rec_select_kernel<T>,
+  hipError_t e = hipFuncSetAttribute((const void*)rec_select_kernel<T, Mode>,
                                      hipFuncAttributeMaxDynamicSharedMemorySize,
                                      rec_lds_bytes<T>());
   if (e != hipSuccess) return e;
@@ -393,9 +451,10 @@ hipError_t recommend(const RecArgs<T>& a0, hipStream_t s) {
     a.t_base = g0 * RC_UG;
     a.nbatch = ng * RC_UG;
     const int64_t nu = a.nreq - a.t_base < a.nbatch ? a.nreq - a.t_base : a.nbatch;
-    hipLaunchKernelGGL(rec_users_kernel<T>, dim3((unsigned)a.nbatch), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(rec_select_kernel<T>, dim3((unsigned)nchunk, (unsigned)ng), dim3(256),
-                       rec_lds_bytes<T>(), s, a);
+    hipLaunchKernelGGL(rec_users_kernel<T>, dim3((unsigned)a.nbatch), dim3(256), 0, s,
+                       static_cast<const RecArgs<T>&>(a));
+    hipLaunchKernelGGL((rec_select_kernel<T, Mode>), dim3((unsigned)nchunk, (unsigned)ng),
+                       dim3(256), rec_lds_bytes<T>(), s, a);
     const RecMergeArgs m{a.part_score, a.part_item, a.part_cnt, nchunk, a.nbatch, a.t_base,
                          a.nreq,       a.topn,      a.items,    a.scores, a.counts};
     hipLaunchKernelGGL(rec_merge_kernel, dim3((unsigned)nu), dim3(64), 0, s, m);
@@ -405,9 +464,36 @@ hipError_t recommend(const RecArgs<T>& a0, hipStream_t s) {
   return hipSuccess;
 }
 
+template <typename T>
+hipError_t similar(const SimArgs<T>& a, hipStream_t s) {
+  return a.cosine ? select<T, SEL_SIM_COSINE>(a, s) : select<T, SEL_SIM_DOT>(a, s);
+}
+
+template <typename T>
+hipError_t factor_norms(const T* F, int64_t n, int k, int kp, double* norms, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(rec_norms_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, F, n,
+                     k, kp, norms);
+  return hipGetLastError();
+}
+
 }  // namespace
 
-hipError_t launch_recommend(const RecArgs<float>& a, hipStream_t s) { return recommend(a, s); }
-hipError_t launch_recommend(const RecArgs<double>& a, hipStream_t s) { return recommend(a, s); }
+hipError_t launch_recommend(const RecArgs<float>& a, hipStream_t s) {
+  return select<float, SEL_RECOMMEND>(a, s);
+}
+hipError_t launch_recommend(const RecArgs<double>& a, hipStream_t s) {
+  return select<double, SEL_RECOMMEND>(a, s);
+}
+hipError_t launch_similar(const SimArgs<float>& a, hipStream_t s) { return similar(a, s); }
+hipError_t launch_similar(const SimArgs<double>& a, hipStream_t s) { return similar(a, s); }
+hipError_t launch_factor_norms(const float* F, int64_t n, int k, int kp, double* norms,
+                               hipStream_t s) {
+  return factor_norms(F, n, k, kp, norms, s);
+}
+hipError_t launch_factor_norms(const double* F, int64_t n, int k, int kp, double* norms,
+                               hipStream_t s) {
+  return factor_norms(F, n, k, kp, norms, s);
+}
 
 }  // namespace qmfx

@@ -165,65 +165,111 @@ void Engine::saveFactors(const FactorData& factorData, const IdIndex& index,
   saveFactors(factorData, index, fout);
 }
 
+std::vector<int64_t> Engine::queryRows(const IdIndex& index, const std::vector<int64_t>* ids,
+                                       const char* what) {
+  std::vector<int64_t> rows;
+  if (ids) {
+    size_t unknown = 0;
+    for (const int64_t id : *ids) {
+      const size_t r = index.idx(id);
+      if (r == IdIndex::missingIdx)
+        ++unknown;
+      else
+        rows.push_back(static_cast<int64_t>(r));
+    }
+    if (unknown > 0)
+      LOG(WARNING) << unknown << " requested " << what
+                   << " ids are not in the training data; skipped";
+  } else {
+    rows.resize(index.size());
+    for (size_t r = 0; r < rows.size(); ++r) rows[r] = static_cast<int64_t>(r);
+  }
+  return rows;
+}
+
+void Engine::formatPairs(const IdIndex& queryIndex, const IdIndex& otherIndex,
+                         const int64_t* rows, const size_t b, const size_t e, const size_t topN,
+                         const int64_t* others, const double* scores, const int32_t* counts,
+                         std::string& s) {
+  char buf[32];
+  for (size_t t = b; t < e; ++t) {
+    const long long qid = static_cast<long long>(queryIndex.id(static_cast<size_t>(rows[t])));
+    for (int32_t r = 0; r < counts[t]; ++r) {
+      s.append(buf, std::to_chars(buf, buf + sizeof(buf), qid).ptr);
+      s.push_back(' ');
+      const size_t other = static_cast<size_t>(others[t * topN + r]);
+      s.append(buf, std::to_chars(buf, buf + sizeof(buf),
+                                  static_cast<long long>(otherIndex.id(other))).ptr);
+      appendFixed9(s, scores[t * topN + r]);
+      s.push_back('\n');
+    }
+  }
+}
+
+namespace {
+
+// The batches of a save call: `select` fills one batch's lists (n queries from rows + r0),
+// which are formatted in blocks in parallel and written in order.
+template <typename Select>
+void savePairs(const IdIndex& queryIndex, const IdIndex& otherIndex,
+               const std::vector<int64_t>& rows, const std::string& fileName, const size_t topN,
+               const Select& select) {
+  std::ofstream fout(fileName);
+  const size_t batch = 65536, block = 4096;
+  const unsigned hc = std::thread::hardware_concurrency();
+  const size_t nt = std::max<size_t>(1, std::min<size_t>(hc ? hc : 1, batch / block));
+  std::vector<int64_t> others(std::min(batch, rows.size()) * topN);
+  std::vector<double> scores(others.size());
+  std::vector<int32_t> counts(std::min(batch, rows.size()));
+  for (size_t r0 = 0; r0 < rows.size(); r0 += batch) {
+    const size_t n = std::min(batch, rows.size() - r0);
+    select(rows.data() + r0, n, others.data(), scores.data(), counts.data());
+    const size_t nblocks = (n + block - 1) / block;
+    for (size_t b0 = 0; b0 < nblocks; b0 += nt) {
+      const size_t nb = std::min(nt, nblocks - b0);
+      std::vector<std::string> parts(nb);
+      ParallelExecutor::run(nb, [&](const size_t p) {
+        const size_t b = (b0 + p) * block, e = std::min(n, b + block);
+        Engine::formatPairs(queryIndex, otherIndex, rows.data() + r0, b, e, topN, others.data(),
+                            scores.data(), counts.data(), parts[p]);
+      });
+      for (const auto& p : parts) fout.write(p.data(), static_cast<std::streamsize>(p.size()));
+    }
+  }
+}
+
+}  // namespace
+
 void Engine::saveRecommendations(qmfx_ctx* ctx, const int exclude, const bool useBiases,
                                  const IdIndex& userIndex, const IdIndex& itemIndex,
                                  const std::string& fileName, const size_t topN,
                                  const std::vector<int64_t>* userIds) {
   CHECK(topN >= 1 && topN <= QMFX_REC_MAX_N)
       << "the number of recommendations must be in 1.." << QMFX_REC_MAX_N << ", got " << topN;
-  std::vector<int64_t> users;
-  if (userIds) {
-    size_t unknown = 0;
-    for (const int64_t id : *userIds) {
-      const size_t u = userIndex.idx(id);
-      if (u == IdIndex::missingIdx)
-        ++unknown;
-      else
-        users.push_back(static_cast<int64_t>(u));
-    }
-    if (unknown > 0)
-      LOG(WARNING) << unknown << " requested user ids are not in the training data; skipped";
-  } else {
-    users.resize(userIndex.size());
-    for (size_t u = 0; u < users.size(); ++u) users[u] = static_cast<int64_t>(u);
-  }
-  std::ofstream fout(fileName);
-  const size_t batch = 65536, block = 4096;
-  const unsigned hc = std::thread::hardware_concurrency();
-  const size_t nt = std::max<size_t>(1, std::min<size_t>(hc ? hc : 1, batch / block));
-  std::vector<int64_t> items(std::min(batch, users.size()) * topN);
-  std::vector<double> scores(items.size());
-  std::vector<int32_t> counts(std::min(batch, users.size()));
-  for (size_t u0 = 0; u0 < users.size(); u0 += batch) {
-    const size_t n = std::min(batch, users.size() - u0);
-    QMFX_CHECK(qmfx_recommend(ctx, static_cast<int64_t>(n), users.data() + u0,
-                              static_cast<int>(topN), exclude, useBiases ? 1 : 0, items.data(),
-                              scores.data(), counts.data()));
-    // format blocks of users in parallel, write them in order
-    const size_t nblocks = (n + block - 1) / block;
-    for (size_t b0 = 0; b0 < nblocks; b0 += nt) {
-      const size_t nb = std::min(nt, nblocks - b0);
-      std::vector<std::string> parts(nb);
-      ParallelExecutor::run(nb, [&](const size_t p) {
-        char buf[32];
-        std::string& s = parts[p];
-        const size_t b = (b0 + p) * block, e = std::min(n, b + block);
-        for (size_t t = b; t < e; ++t) {
-          const long long uid = static_cast<long long>(userIndex.id(static_cast<size_t>(users[u0 + t])));
-          for (int32_t r = 0; r < counts[t]; ++r) {
-            s.append(buf, std::to_chars(buf, buf + sizeof(buf), uid).ptr);
-            s.push_back(' ');
-            const size_t item = static_cast<size_t>(items[t * topN + r]);
-            s.append(buf, std::to_chars(buf, buf + sizeof(buf),
-                                        static_cast<long long>(itemIndex.id(item))).ptr);
-            appendFixed9(s, scores[t * topN + r]);
-            s.push_back('\n');
-          }
-        }
-      });
-      for (const auto& p : parts) fout.write(p.data(), static_cast<std::streamsize>(p.size()));
-    }
-  }
+  const std::vector<int64_t> users = queryRows(userIndex, userIds, "user");
+  savePairs(userIndex, itemIndex, users, fileName, topN,
+            [&](const int64_t* rows, const size_t n, int64_t* items, double* scores,
+                int32_t* counts) {
+              QMFX_CHECK(qmfx_recommend(ctx, static_cast<int64_t>(n), rows,
+                                        static_cast<int>(topN), exclude, useBiases ? 1 : 0,
+                                        items, scores, counts));
+            });
+}
+
+void Engine::saveSimilarities(qmfx_ctx* ctx, const int side, const IdIndex& index,
+                              const std::string& fileName, const size_t topN, const bool cosine,
+                              const std::vector<int64_t>* ids) {
+  CHECK(topN >= 1 && topN <= QMFX_REC_MAX_N)
+      << "the number of similar rows must be in 1.." << QMFX_REC_MAX_N << ", got " << topN;
+  const std::vector<int64_t> rows = queryRows(index, ids, side == QMFX_USERS ? "user" : "item");
+  savePairs(index, index, rows, fileName, topN,
+            [&](const int64_t* q, const size_t n, int64_t* neighbours, double* scores,
+                int32_t* counts) {
+              QMFX_CHECK(qmfx_similar(ctx, side, static_cast<int64_t>(n), q,
+                                      static_cast<int>(topN),
+                                      cosine ? QMFX_SIM_COSINE : QMFX_SIM_DOT, 1, neighbours,
+                                      scores, counts));
+            });
 }
 
 void Engine::saveFactors(const FactorData& factorData, const IdIndex& index, std::ostream& out) {

@@ -40,6 +40,31 @@ class Engine {
   // out; a user with no eligible item writes nothing.
   virtual void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
                                        const std::vector<int64_t>* userIds = nullptr) const {}
+  // Addition to the reference API: the topN (1..QMFX_REC_MAX_N) nearest items of every item
+  // (ascending item idx), or of the items in `itemIds` in that order (unknown ids are skipped
+  // with one warning), among the items, by cosine (else by dot product) of the current factors,
+  // selected on the device (include/qmfx.h qmfx_similar).  One line "<id> <neighbourId>
+  // <score>\n" per pair, scores with 9 decimals, each query's lines in rank order (higher
+  // score first, equal scores by ascending idx): the dataset format.  The query itself is
+  // always left out.  saveUserSimilarities: the same for users among the users.
+  virtual void saveItemSimilarities(const std::string& fileName, size_t topN, bool cosine,
+                                    const std::vector<int64_t>* itemIds = nullptr) const {}
+  virtual void saveUserSimilarities(const std::string& fileName, size_t topN, bool cosine,
+                                    const std::vector<int64_t>* userIds = nullptr) const {}
+
+  // The query rows of a save call: the idx of every id of `ids` that `index` knows, in that
+  // order (the others are skipped with one warning carrying their count, `what` naming them),
+  // or every idx ascending when ids is null.
+  static std::vector<int64_t> queryRows(const IdIndex& index, const std::vector<int64_t>* ids,
+                                        const char* what);
+
+  // Appends "<queryId> <otherId> <score>\n" (%.9f) for queries [b, e) of a batch: query t is
+  // idx rows[t] of queryIndex and lists others[t·topN + r] (idx of otherIndex) with
+  // scores[t·topN + r] for r < counts[t].
+  static void formatPairs(const IdIndex& queryIndex, const IdIndex& otherIndex,
+                          const int64_t* rows, size_t b, size_t e, size_t topN,
+                          const int64_t* others, const double* scores, const int32_t* counts,
+                          std::string& s);
 
  protected:
   // saveUserRecommendations of the engines: qmfx_recommend (include/qmfx.h) with the given
@@ -48,6 +73,12 @@ class Engine {
                                   const IdIndex& userIndex, const IdIndex& itemIndex,
                                   const std::string& fileName, size_t topN,
                                   const std::vector<int64_t>* userIds);
+
+  // save{Item,User}Similarities of the engines: qmfx_similar on `side` (whose id table is
+  // `index`) in batches of at most 65,536 queries, written batch by batch
+  static void saveSimilarities(qmfx_ctx* ctx, int side, const IdIndex& index,
+                               const std::string& fileName, size_t topN, bool cosine,
+                               const std::vector<int64_t>* ids);
 
   // test users (those with at least one known (user, item) test pair), optionally a
   // sample of numTestUsers of them shuffled with mt19937(seed), and their dense label rows

@@ -232,4 +232,16 @@ void BPREngine::saveUserRecommendations(const std::string& fileName, const size_
                       config_.useBiases, userIndex_, itemIndex_, fileName, topN, userIds);
 }
 
+void BPREngine::saveItemSimilarities(const std::string& fileName, const size_t topN,
+                                  const bool cosine, const std::vector<int64_t>* itemIds) const {
+  CHECK(dev_) << "no factor data, have you initialized the engine?";
+  saveSimilarities(dev_->get(), QMFX_ITEMS, itemIndex_, fileName, topN, cosine, itemIds);
+}
+
+void BPREngine::saveUserSimilarities(const std::string& fileName, const size_t topN,
+                                  const bool cosine, const std::vector<int64_t>* userIds) const {
+  CHECK(dev_) << "no factor data, have you initialized the engine?";
+  saveSimilarities(dev_->get(), QMFX_USERS, userIndex_, fileName, topN, cosine, userIds);
+}
+
 }  // namespace qmf

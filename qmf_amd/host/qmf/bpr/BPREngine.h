@@ -63,6 +63,11 @@ class BPREngine : public Engine {
   // biases when the model uses them
   void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
                                const std::vector<int64_t>* userIds = nullptr) const override;
+  // the query itself is always left out; item biases are never part of a similarity
+  void saveItemSimilarities(const std::string& fileName, size_t topN, bool cosine,
+                            const std::vector<int64_t>* itemIds = nullptr) const override;
+  void saveUserSimilarities(const std::string& fileName, size_t topN, bool cosine,
+                            const std::vector<int64_t>* userIds = nullptr) const override;
 
   // --- additions (not in the reference API) ---
   struct PosNegTriplet {

@@ -190,6 +190,18 @@ void WALSEngine::saveUserRecommendations(const std::string& fileName, const size
                       userIndex_, itemIndex_, fileName, topN, userIds);
 }
 
+void WALSEngine::saveItemSimilarities(const std::string& fileName, const size_t topN,
+                                  const bool cosine, const std::vector<int64_t>* itemIds) const {
+  CHECK(dev_) << "no factor data, have you initialized the engine?";
+  saveSimilarities(dev_->get(), QMFX_ITEMS, itemIndex_, fileName, topN, cosine, itemIds);
+}
+
+void WALSEngine::saveUserSimilarities(const std::string& fileName, const size_t topN,
+                                  const bool cosine, const std::vector<int64_t>* userIds) const {
+  CHECK(dev_) << "no factor data, have you initialized the engine?";
+  saveSimilarities(dev_->get(), QMFX_USERS, userIndex_, fileName, topN, cosine, userIds);
+}
+
 size_t WALSEngine::nusers() const { return userIndex_.size(); }
 size_t WALSEngine::nitems() const { return itemIndex_.size(); }
 

@@ -53,6 +53,11 @@ class WALSEngine : public Engine {
   // includeSeen = false leaves out the items of the user's training signals (one GPU only)
   void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
                                const std::vector<int64_t>* userIds = nullptr) const override;
+  // the query itself is always left out; with several GPUs rank 0 answers (full replicas)
+  void saveItemSimilarities(const std::string& fileName, size_t topN, bool cosine,
+                            const std::vector<int64_t>* itemIds = nullptr) const override;
+  void saveUserSimilarities(const std::string& fileName, size_t topN, bool cosine,
+                            const std::vector<int64_t>* userIds = nullptr) const override;
 
   // --- additions (not in the reference API) ---
   // host copies of the current factors (synchronised from the device on access)

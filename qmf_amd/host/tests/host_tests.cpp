@@ -589,4 +589,77 @@ TEST(BPR, userWithEveryItemAborts) {
   EXPECT_DEATH(BPREngineTestPeer::initHost(e, d));
 }
 
+// ---- similar rows: the id-list reader, the id -> idx mapping and the pair writer ------------
+TEST(Similar, readIds) {
+  const std::string path = tmpPath("ids");
+  {
+    std::ofstream f(path);
+    f << "7\n-3\r\n\n12 \n9223372036854775807\n";
+  }
+  EXPECT_TRUE(readIds(path) == std::vector<int64_t>({7, -3, 12, 9223372036854775807ll}));
+  {
+    std::ofstream f(path);
+    f << "7\n8x\n";
+  }
+  EXPECT_DEATH(readIds(path));
+  std::remove(path.c_str());
+  EXPECT_DEATH(readIds(path));
+}
+
+TEST(Similar, queryRows) {
+  IdIndex index;  // first-appearance order, as BPR builds it
+  for (const int64_t id : {50, -2, 7, 19}) index.getOrSetIdx(id);
+  EXPECT_TRUE(Engine::queryRows(index, nullptr, "item") == std::vector<int64_t>({0, 1, 2, 3}));
+  // the list's order, repeats kept, unknown ids skipped
+  const std::vector<int64_t> ids = {19, 1000, 50, 19, -7};
+  EXPECT_TRUE(Engine::queryRows(index, &ids, "item") == std::vector<int64_t>({3, 0, 3}));
+  const std::vector<int64_t> none;
+  EXPECT_TRUE(Engine::queryRows(index, &none, "item").empty());
+}
+
+TEST(Similar, formatPairs) {
+  IdIndex index;
+  index.assignSorted({-5, 10, 11, 4000000000ll});
+  const size_t topN = 3;
+  const std::vector<int64_t> rows = {2, 0, 3};
+  // query 0 (idx 2) lists two neighbours, query 1 none, query 2 three; unused slots are -1 / 0.0
+  const std::vector<int64_t> others = {3, 0, -1, -1, -1, -1, 0, 1, 2};
+  const std::vector<double> scores = {1.0, -0.1234567895, 0.0, 0.0, 0.0, 0.0, 2.5e-10, -0.0, -7.25};
+  const std::vector<int32_t> counts = {2, 0, 3};
+  std::string all;
+  Engine::formatPairs(index, index, rows.data(), 0, 3, topN, others.data(), scores.data(),
+                      counts.data(), all);
+  // every score as printf("%.9f") renders it
+  std::string want;
+  char buf[128];
+  const int64_t q[5] = {11, 11, 4000000000ll, 4000000000ll, 4000000000ll};
+  const int64_t o[5] = {4000000000ll, -5, -5, 10, 11};
+  const double v[5] = {1.0, -0.1234567895, 2.5e-10, -0.0, -7.25};
+  for (int j = 0; j < 5; ++j) {
+    std::snprintf(buf, sizeof(buf), "%lld %lld %.9f\n", (long long)q[j], (long long)o[j], v[j]);
+    want += buf;
+  }
+  EXPECT_TRUE(all == want);
+  EXPECT_TRUE(all.find("11 4000000000 1.000000000\n") == 0);
+  // a sub-range appends only its queries, behind what the string holds
+  std::string part = "x";
+  Engine::formatPairs(index, index, rows.data(), 1, 2, topN, others.data(), scores.data(),
+                      counts.data(), part);
+  EXPECT_TRUE(part == "x");
+  Engine::formatPairs(index, index, rows.data(), 2, 3, topN, others.data(), scores.data(),
+                      counts.data(), part);
+  EXPECT_TRUE(part == "x" + want.substr(want.find("4000000000 -5")));
+  // the lines are the dataset format: DatasetReader reads them back
+  const std::string path = tmpPath("pairs");
+  {
+    std::ofstream f(path);
+    f << all;
+  }
+  const auto back = DatasetReader(path).readAll();
+  EXPECT_EQ(back.size(), (size_t)5);
+  EXPECT_TRUE(back[1].userId == 11 && back[1].itemId == -5);
+  EXPECT_NEAR(back[1].value, -0.1234567895, 5.0000001e-10);  // nine decimals
+  std::remove(path.c_str());
+}
+
 int main(int argc, char** argv) { return testing::runAll(argc, argv); }

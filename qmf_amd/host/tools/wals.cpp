@@ -1,7 +1,9 @@
 // `wals` command line, drop-in for the reference's qmf/wals.cpp:26-107: same flags, same
 // log lines and output files.  Additions: --device, --precision (32 | 64), --ngpus, and the
 // top-N recommendations of the trained model: --user_recommendations, --num_recommendations,
-// --recommend_seen, --recommend_users.
+// --recommend_seen, --recommend_users; and the items' / users' nearest neighbours in factor
+// space: --item_similarities, --user_similarities, --num_similar, --similarity,
+// --similar_item_ids, --similar_user_ids.
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -48,6 +50,15 @@ DEFINE_uint64(num_recommendations, 10, "items recommended per user (1..128)");
 DEFINE_bool(recommend_seen, false, "also recommend items of the user's training data");
 DEFINE_string(recommend_users, "",
               "file with one user id per line to recommend for (default: every training user)");
+// similar items / users (nearest neighbours in factor space)
+DEFINE_string(item_similarities, "", "filename of the items' top-N most similar items");
+DEFINE_string(user_similarities, "", "filename of the users' top-N most similar users");
+DEFINE_uint64(num_similar, 10, "neighbours listed per item or user (1..128)");
+DEFINE_string(similarity, "cosine", "similarity of two factor rows: cosine or dot");
+DEFINE_string(similar_item_ids, "",
+              "file with one item id per line to list neighbours for (default: every item)");
+DEFINE_string(similar_user_ids, "",
+              "file with one user id per line to list neighbours for (default: every user)");
 
 namespace {
 // QMF_TIMINGS=1 (an addition; unset, the output is the reference's): one "timing:" log line per
@@ -84,6 +95,11 @@ int main(int argc, char** argv) {
   if (!FLAGS_user_recommendations.empty())
     CHECK(FLAGS_num_recommendations >= 1 && FLAGS_num_recommendations <= QMFX_REC_MAX_N)
         << "--num_recommendations must be in 1.." << QMFX_REC_MAX_N;
+  CHECK(FLAGS_similarity == "cosine" || FLAGS_similarity == "dot")
+      << "--similarity must be cosine or dot";
+  if (!FLAGS_item_similarities.empty() || !FLAGS_user_similarities.empty())
+    CHECK(FLAGS_num_similar >= 1 && FLAGS_num_similar <= QMFX_REC_MAX_N)
+        << "--num_similar must be in 1.." << QMFX_REC_MAX_N;
   qmf::DeviceOptions device;
   device.device = FLAGS_device;
   device.precision = FLAGS_precision;
@@ -131,6 +147,26 @@ int main(int argc, char** argv) {
     if (timings())
       LOG(INFO) << "timing: recommend " << now() - t0 << " s, "
                 << fileBytes(FLAGS_user_recommendations) << " bytes";
+  }
+  if (!FLAGS_item_similarities.empty() || !FLAGS_user_similarities.empty()) {
+    LOG(INFO) << "saving similarities";
+    t0 = now();
+    const bool cosine = FLAGS_similarity == "cosine";
+    std::vector<int64_t> ids;
+    if (!FLAGS_item_similarities.empty()) {
+      if (!FLAGS_similar_item_ids.empty()) ids = qmf::readIds(FLAGS_similar_item_ids);
+      engine.saveItemSimilarities(FLAGS_item_similarities, FLAGS_num_similar, cosine,
+                                  FLAGS_similar_item_ids.empty() ? nullptr : &ids);
+    }
+    if (!FLAGS_user_similarities.empty()) {
+      if (!FLAGS_similar_user_ids.empty()) ids = qmf::readIds(FLAGS_similar_user_ids);
+      engine.saveUserSimilarities(FLAGS_user_similarities, FLAGS_num_similar, cosine,
+                                  FLAGS_similar_user_ids.empty() ? nullptr : &ids);
+    }
+    if (timings())
+      LOG(INFO) << "timing: similar " << now() - t0 << " s, "
+                << fileBytes(FLAGS_item_similarities) + fileBytes(FLAGS_user_similarities)
+                << " bytes";
   }
   return 0;
 }
