@@ -49,6 +49,9 @@ int qmfx_device_count(int* count);
 int qmfx_create(qmfx_ctx** out, int device, int precision, int nfactors);
 int qmfx_destroy(qmfx_ctx* ctx);
 int qmfx_sync(qmfx_ctx* ctx);
+/* A changed row count releases what the old one sized or indexed: that side's factors and
+   CSR; with either side, the test labels, the BPR positives and the cached qmfx_bpr_eval
+   triplets; with the item count, the item biases.  The same shape again keeps all of these. */
 int qmfx_set_shape(qmfx_ctx* ctx, int64_t nusers, int64_t nitems);
 int qmfx_get_shape(qmfx_ctx* ctx, int64_t* nusers, int64_t* nitems, int64_t* nnz);
 

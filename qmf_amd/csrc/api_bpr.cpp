@@ -67,6 +67,22 @@ const char* const kBadGradients =
 
 }  // namespace
 
+// The positives index both sides' rows and urowptr is sized from the user count; the cached
+// triplets of qmfx_bpr_eval were range-checked against the shape they were uploaded under.
+void qmfx::drop_bpr_positives(qmfx_ctx* c) {
+  c->pos_user.reset();
+  c->pos_item.reset();
+  c->urowptr.reset();
+  c->uitems.reset();
+  c->npos = 0;
+  c->max_user_pos = 0;
+  for (int slot = 0; slot < 2; ++slot) {
+    c->trip[slot].reset();
+    c->trip_src[slot] = nullptr;
+    c->trip_n[slot] = 0;
+  }
+}
+
 extern "C" {
 
 int qmfx_bpr_set_positives(qmfx_ctx* c, const int64_t* users, const int64_t* items, int64_t npos) {
@@ -196,6 +212,10 @@ int qmfx_bpr_eval(qmfx_ctx* c, int slot, const int64_t* trip, int64_t n, int use
                   double* loss_sum) {
   if (slot != 0 && slot != 1) return fail("slot must be 0 or 1");
   if (set_dev(c)) return -2;
+  // (a changed shape releases the factors and the biases: zero again, as qmfx_bpr_apply's)
+  if (int rc = ensure_side_factors(c, 0)) return rc;
+  if (int rc = ensure_side_factors(c, 1)) return rc;
+  if (int rc = ensure_bias(c)) return rc;
   if (c->trip_src[slot] != (const void*)trip || c->trip_n[slot] != n) {
     if (!triplets_in_range(c, trip, n)) return fail("triplet index out of range");
     HIPCHK(dev_alloc(c->trip[slot], (size_t)std::max<int64_t>(n, 1) * 24));

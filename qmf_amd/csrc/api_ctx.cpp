@@ -100,6 +100,7 @@ int qmfx_set_shape(qmfx_ctx* c, int64_t nusers, int64_t nitems) {
   if (nusers <= 0 || nitems <= 0) return fail("empty shape: nusers and nitems must be > 0");
   if (nitems > 0x7fffffffll || nusers > 0x7fffffffll) return fail("more than 2^31 rows");
   if (set_dev(c)) return -2;
+  const bool users_changed = c->s[0].n != nusers, items_changed = c->s[1].n != nitems;
   for (int side = 0; side < 2; ++side) {
     const int64_t n = side == 0 ? nusers : nitems;
     c->s[side].h_ids.clear();
@@ -107,9 +108,18 @@ int qmfx_set_shape(qmfx_ctx* c, int64_t nusers, int64_t nitems) {
       c->s[side].F.reset();
       drop_csr(c->s[side]);
       c->s[side].h_rowptr.clear();
+      c->s[side].buckets_valid = false;
       c->s[side].n = n;
     }
   }
+  // What was sized or indexed by the old row counts goes with them; a call that needs it
+  // fails until it is set again (scratch behind a capacity check, such as rowloss, Z and the
+  // rc_* buffers, regrows on demand and stays).
+  if (users_changed || items_changed) {
+    drop_eval_labels(c);
+    drop_bpr_positives(c);
+  }
+  if (items_changed) c->bias.reset();
   return 0;
 }
 

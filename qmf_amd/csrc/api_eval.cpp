@@ -27,6 +27,22 @@ static EvalArgs<T> eval_args(qmfx_ctx* c, int use_biases) {
   return a;
 }
 
+// The label set indexes both sides' rows, and ev_sq / ev_chunks are sized from the item count:
+// a new label set and a changed shape (qmfx_set_shape) both start from none.
+void qmfx::drop_eval_labels(qmfx_ctx* c) {
+  c->ev_users.reset();
+  c->ev_slot.reset();
+  c->ev_item.reset();
+  c->ev_pidx.reset();
+  c->ev_pptr.reset();
+  c->ev_lscore.reset();
+  c->ev_pscore.reset();
+  c->ev_above.reset();
+  c->ev_sq.reset();
+  c->ev_udbl.reset();
+  c->ev_ntest = c->ev_nlab = c->ev_npos = c->ev_chunks = 0;
+}
+
 extern "C" {
 
 int qmfx_eval_set_labels(qmfx_ctx* c, int64_t ntest, const int64_t* users, const int64_t* rowptr,
@@ -54,16 +70,7 @@ int qmfx_eval_set_labels(qmfx_ctx* c, int64_t ntest, const int64_t* users, const
   pptr[(size_t)ntest] = np;
   const int64_t nch = eval_chunks(ntest, ni);
   // the previous label set goes before the new one is allocated
-  c->ev_users.reset();
-  c->ev_slot.reset();
-  c->ev_item.reset();
-  c->ev_pidx.reset();
-  c->ev_pptr.reset();
-  c->ev_lscore.reset();
-  c->ev_pscore.reset();
-  c->ev_above.reset();
-  c->ev_sq.reset();
-  c->ev_udbl.reset();
+  drop_eval_labels(c);
   const size_t nl = (size_t)std::max<int64_t>(nlab, 1), npp = (size_t)std::max<int64_t>(np, 1);
   HIPCHK(dev_alloc(c->ev_users, (size_t)std::max<int64_t>(ntest, 1) * 8));
   HIPCHK(dev_alloc(c->ev_slot, nl * 4));

@@ -401,6 +401,7 @@ int qmfx_wals_row_losses(qmfx_ctx* c, double* out) {
 
 int qmfx_wals_failed_rows(qmfx_ctx* c, int64_t* rows, int64_t cap, int64_t* count) {
   SideBuf& L = c->s[c->last_side];
+  if (!c->status || c->rowloss_cap < L.n) return fail("no half solved yet");
   if (set_dev(c)) return -2;
   std::vector<int32_t> st((size_t)std::max<int64_t>(L.n, 1));
   HIPCHK(scopy(c, st.data(), c->status, st.size() * 4, hipMemcpyDeviceToHost));

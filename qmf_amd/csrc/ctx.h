@@ -400,4 +400,9 @@ void plan_pieces(const std::vector<int64_t>& rp, const std::vector<int64_t>& bou
 int build_buckets(qmfx_ctx* c, int side);
 int shard_csr(qmfx_ctx* c, SideBuf& sb);
 
+// api_eval.cpp
+void drop_eval_labels(qmfx_ctx* c);  // releases the test-label set (qmfx_eval_ranks then fails)
+// api_bpr.cpp
+void drop_bpr_positives(qmfx_ctx* c);  // releases the positives (qmfx_bpr_epoch then fails)
+
 }  // namespace qmfx

@@ -239,3 +239,48 @@ def bpr_linear_item(trip, U0, lr, nitems):
     np.add.at(b, trip[:, 1], 0.5 * lr)
     np.add.at(b, trip[:, 2], -0.5 * lr)
     return I, b
+
+
+# ---- test-set evaluation (qmf_amd/csrc/eval.hip): the reference of tests/test_eval_edges_gpu.py,
+# anchored on pyoracle by tests/test_eval.py
+def eval_scores(U, I, users, bias=None):
+    """pyoracle.test_scores over all the users at once: S = bias (or 0), then
+    S = S + U[users, f, None] * I[None, :, f] in factor order.  Elementwise multiply then add,
+    each rounded (no fused multiply-add), so row t is test_scores' row t bit for bit."""
+    U = np.asarray(U, np.float64)
+    I = np.asarray(I, np.float64)
+    users = np.asarray(users, np.int64)
+    S = np.zeros((len(users), I.shape[0]))
+    if bias is not None:  # copied, not added to the zeros: a bias of -0.0 stays -0.0
+        S[:] = np.asarray(bias, np.float64)[None, :]
+    for f in range(I.shape[1]):
+        S = S + U[users, f, None] * I[None, :, f]
+    return S
+
+
+def eval_reference(S, rows, rowptr, items, values):
+    """What qmfx_eval_ranks returns, by brute force, for test slots whose scores are the rows
+    S[rows[t]] (a user may fill several slots) and whose labels are the CSR (rowptr, items,
+    values): the score of every labelled pair, for every positive label (value > 0, in label
+    order, a repeated item counted each time) the number of items scored strictly higher, and
+    Σ score² per slot."""
+    rows = np.asarray(rows, np.int64)
+    items = np.asarray(items, np.int64)
+    r = rows[np.repeat(np.arange(len(rows)), np.diff(rowptr))]
+    ls = S[r, items]
+    above = np.array([np.count_nonzero(S[r[e]] > S[r[e], items[e]])
+                      for e in np.nonzero(np.asarray(values) > 0)[0]], np.int64)
+    sq = np.array([np.sum(S[u] ** 2) for u in range(len(S))])[rows]
+    return ls, above, sq
+
+
+def eval_chunks(ntest, nitems):
+    """(chunks, items per chunk) of the rank kernel's grid: eval.hip's eval_chunks and the
+    chunk length eval_ranks derives from it, restated (32 users per group, 64 items per tile,
+    about 4096 workgroups)."""
+    groups = -(-ntest // 32)
+    tiles = -(-nitems // 64)
+    n = max(1, min(4096 // max(groups, 1), tiles))
+    chunk = -(-(-(-nitems // n)) // 64) * 64
+    n = -(-nitems // chunk)
+    return n, -(-(-(-nitems // n)) // 64) * 64
