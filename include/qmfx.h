@@ -222,6 +222,54 @@ int qmfx_similar(qmfx_ctx* ctx, int side, int64_t nq, const int64_t* rows, int t
                  int exclude_self, int64_t* neighbours /*nq·topn*/, double* scores /*nq·topn*/,
                  int32_t* counts /*nq*/);
 
+/* ---- fold-in: rows that were not in the training matrix ------------------------------------
+ * qmfx_wals_fold_in solves nrows new rows of `side` against the context's current factors of
+ * the other side.  The rows come as a CSR of their own: rowptr[nrows+1], colidx = row idx on
+ * the other side, values.  Row r's x is what qmfx_wals_half(side) would write for a row with
+ * these signals: the same formulas and row kernels, the context precision, the same pivoted
+ * fp64 re-solve of a row the Cholesky kernels flag (*pivoted counts them), and -6 when a row is
+ * exactly singular.  factors[r*k + f] carries the values the device holds, widened (an fp32
+ * context's rounding is visible, as in qmfx_get_factors); losses[r] is the row's term of a
+ * half's *loss_sum.  A row without signals is exactly 0; repeated columns within a row add up,
+ * as duplicate pairs do in training.
+ * The context needs the shape and the other side's factors only (qmfx_set_shape +
+ * qmfx_set_factors): neither a CSR nor factors of `side`.  The call leaves the context's
+ * factors, CSR, row buckets and everything qmfx_wals_row_losses / qmfx_wals_failed_rows report
+ * about the last half untouched: the new rows, their losses and status words live in scratch
+ * of their own, grown on demand.  YᵀY, the whitening of the fixed side and G + λI's image are
+ * computed by every call, never cached (they overwrite the buffers every half recomputes).
+ * The rows' plan (whitened buckets and direct rows, the limits of qmfx_row_classes;
+ * QMFX_NO_WHITEN and QMFX_WB_K64_NTN act as on training) is built on the device; rows of any
+ * length are solved whole, never split into segments.  Works on any rank of a sharded context,
+ * the factors being full replicas.
+ * Fails (-1, with a message, before anything is launched) on: side not 0 or 1, no factors on
+ * the fixed side, rowptr[0] != 0 or rowptr decreasing, a column index outside the other side,
+ * nrows or rowptr[nrows] >= 2^31.  nrows == 0 succeeds and touches nothing.
+ *
+ * qmfx_fold_in_classes: the bucket counts of the plan the last fold-in call used, laid out
+ * like qmfx_row_classes [0..8]; [9] and [10] are 0.  qmfx_fold_in_order: that plan's
+ * processing order (nrows row indices): the whitened buckets in ascending order with rows
+ * ascending inside each, then the direct rows by descending signal count, ties by ascending
+ * row (what the row buckets of a side hold for the same rows in one piece).
+ *
+ * qmfx_recommend_fold_in (new users only): folds the rows in as side 0, then selects each new
+ * row's top-N as qmfx_recommend defines it: the scores are qmfx_recommend's, bit for bit, on
+ * the device-held folded rows and item factors, without biases; the same order and tie rule;
+ * the unused tail is -1 / 0.0.  exclude_seen != 0 removes the row's own colidx and needs them
+ * ascending within a row (repeats allowed), failing otherwise.  topn is 1..QMFX_REC_MAX_N.
+ * factors (NULL or nrows·k) receives the folded rows. */
+int qmfx_wals_fold_in(qmfx_ctx* ctx, int side, int64_t nrows, const int64_t* rowptr /*nrows+1*/,
+                      const int32_t* colidx, const double* values, double alpha, double lambda,
+                      double* factors /*nrows·k*/, double* losses /*nrows or NULL*/,
+                      int64_t* pivoted /*NULL or: rows re-solved with pivoting*/);
+int qmfx_fold_in_classes(qmfx_ctx* ctx, int64_t* counts /*11*/);
+int qmfx_fold_in_order(qmfx_ctx* ctx, int64_t* order /*nrows of the last call*/);
+int qmfx_recommend_fold_in(qmfx_ctx* ctx, int64_t nrows, const int64_t* rowptr,
+                           const int32_t* colidx, const double* values, double alpha,
+                           double lambda, int topn, int exclude_seen, int64_t* items /*nrows·topn*/,
+                           double* scores /*nrows·topn*/, int32_t* counts /*nrows*/,
+                           double* factors /*NULL or nrows·k*/);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) -------------------------------------- */
 int qmfx_rccl_unique_id(uint8_t* id128);
 /* Joins the RCCL communicator (id128 from rank 0's qmfx_rccl_unique_id), takes this rank's
@@ -253,7 +301,8 @@ int qmfx_dist_plan(const int64_t* rowptr, int64_t nrows, int world, int npieces,
 /* ---- measurement -------------------------------------------------------------------------- */
 /* HIP-event time of the row-solve kernel launches (on the context stream) since reset; the
  * kernels of qmfx_bpr_epoch, qmfx_recommend and qmfx_similar calls are counted here too (one
- * unit of a similar call is 2k flop per (query, row) pair). */
+ * unit of a similar call is 2k flop per (query, row) pair), and those of the fold-in calls
+ * (planning and gather included; the work counted is the k×k form of every row). */
 int qmfx_solve_kernel_stats(qmfx_ctx* ctx, double* total_ms, int64_t* launches,
                             double* flops, double* bytes);
 /* Per kernel class since reset: 0 = direct row kernel, 1 = whitened row kernels (row solve

@@ -59,6 +59,11 @@ SIGNATURES = {
     "qmfx_recommend": [vp, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64, P_i32],
     "qmfx_factor_norms": [vp, c_int, P_f64],
     "qmfx_similar": [vp, c_int, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64, P_i32],
+    "qmfx_wals_fold_in": [vp, c_int, c_i64, P_i64, P_i32, P_f64, c_dbl, c_dbl, P_f64, P_f64, P_i64],
+    "qmfx_fold_in_classes": [vp, P_i64],
+    "qmfx_fold_in_order": [vp, P_i64],
+    "qmfx_recommend_fold_in": [vp, c_i64, P_i64, P_i32, P_f64, c_dbl, c_dbl, c_int, c_int, P_i64,
+                               P_f64, P_i32, P_f64],
     "qmfx_rccl_unique_id": [P_u8],
     "qmfx_dist_init": [vp, c_int, c_int, P_u8],
     "qmfx_partition_rows": [P_i64, c_i64, c_int, c_int, P_i64, P_i64],
@@ -414,6 +419,57 @@ class Context:
                                   int(bool(exclude_self)), _p(neighbours, P_i64),
                                   _p(scores, P_f64), _p(counts, P_i32)))
         return neighbours, scores, counts
+
+    # ---- fold-in
+    @staticmethod
+    def _rows(rowptr, colidx, values):
+        rp = np.ascontiguousarray(rowptr, np.int64)
+        col = np.ascontiguousarray(colidx, np.int32)
+        val = np.ascontiguousarray(values, np.float64)
+        if len(rp) < 1 or len(col) != len(val):
+            raise QmfxError("fold-in CSR shape mismatch")
+        return rp, col, val
+
+    def wals_fold_in(self, side, rowptr, colidx, values, alpha, lam):
+        """(factors[n, k], losses[n], pivoted) of the n = len(rowptr) - 1 new rows of `side`
+        given as a CSR of their own: see include/qmfx.h qmfx_wals_fold_in."""
+        rp, col, val = self._rows(rowptr, colidx, values)
+        n = len(rp) - 1
+        F = np.empty((n, self.k), np.float64)
+        losses = np.empty(n, np.float64)
+        piv = c_i64(0)
+        _check(lib().qmfx_wals_fold_in(self.h, int(side), n, _p(rp, P_i64), _p(col, P_i32),
+                                       _p(val, P_f64), float(alpha), float(lam), _p(F, P_f64),
+                                       _p(losses, P_f64), ctypes.byref(piv)))
+        return F, losses, piv.value
+
+    def fold_in_classes(self):
+        """The last fold-in's row plan, as row_classes reports a side's."""
+        out = np.zeros(11, np.int64)
+        _check(lib().qmfx_fold_in_classes(self.h, _p(out, P_i64)))
+        return {"whitened": out[:8].tolist(), "direct": int(out[8]), "heavy": int(out[9]),
+                "segments": int(out[10])}
+
+    def fold_in_order(self, nrows):
+        """The last fold-in's processing order (its nrows row indices)."""
+        out = np.empty(nrows, np.int64)
+        _check(lib().qmfx_fold_in_order(self.h, _p(out, P_i64)))
+        return out
+
+    def recommend_fold_in(self, rowptr, colidx, values, alpha, lam, topn, exclude_seen=True):
+        """(items[n, topn], scores[n, topn], counts[n], factors[n, k]) of n new users: see
+        include/qmfx.h qmfx_recommend_fold_in."""
+        rp, col, val = self._rows(rowptr, colidx, values)
+        n, w = len(rp) - 1, max(int(topn), 0)
+        items = np.empty((n, w), np.int64)
+        scores = np.empty((n, w), np.float64)
+        counts = np.empty(n, np.int32)
+        F = np.empty((n, self.k), np.float64)
+        _check(lib().qmfx_recommend_fold_in(self.h, n, _p(rp, P_i64), _p(col, P_i32),
+                                            _p(val, P_f64), float(alpha), float(lam), int(topn),
+                                            int(bool(exclude_seen)), _p(items, P_i64),
+                                            _p(scores, P_f64), _p(counts, P_i32), _p(F, P_f64)))
+        return items, scores, counts, F
 
     # ---- dist / stats
     def dist_init(self, rank, world, uid):

@@ -68,25 +68,7 @@ int half_begin_t(qmfx_ctx* c, int side, double alpha, double lambda) {
   const bool use_w = nW > 0 && lambda > 0.0;    // M = YᵀY + λI is SPD only for λ > 0
   c->hs = qmfx_ctx::HalfStateT{side, alpha, lambda, use_w, 0, std::getenv("QMFX_TRACE")};
   HIPCHK(hipEventRecord(c->evh[0], c->stream));
-  // G = YᵀY of the fixed side (full replica on every rank)
-  HIPCHK(launch_gram_t<T>(c, R));
-  if (use_w) {
-    if (c->z_cap < R.n) {
-      // one extra all-zero row (index z_cap): the whitened kernel's padding signals
-      const int64_t cap = std::max(c->s[0].n, c->s[1].n);
-      HIPCHK(dev_alloc(c->Z, (size_t)(cap + 1) * c->kp * c->esz));
-      HIPCHK(hipMemsetAsync(c->Z.as<char>() + (size_t)cap * c->kp * c->esz, 0,
-                            (size_t)c->kp * c->esz, c->stream));
-      c->z_cap = cap;
-    }
-    HIPCHK(hipMemsetAsync(c->chol_status, 0, 4, c->stream));
-    HIPCHK(launch_chol_inv(c->G.as<const T>(), c->nt, c->k, lambda, c->Linv.as<T>(),
-                           c->chol_status, c->chol_scratch, c->stream));
-    HIPCHK(launch_whiten(R.F.as<const T>(), c->Z.as<T>(), nullptr, R.n, c->nt,
-                         c->Linv.as<const T>(), nullptr, 0.0, false, c->cus, c->stream));
-  }
-  if (!use_big_rows(c))
-    HIPCHK(launch_gimg(c->G.as<const T>(), c->nt, c->k, lambda, c->Gimg.as<T>(), c->stream));
+  if (int rc = fixed_side_prologue<T>(c, R, lambda, use_w)) return rc;
   HIPCHK(hipMemsetAsync(c->status, 0, (size_t)std::max<int64_t>(L.n, 1) * sizeof(int32_t), c->stream));
   HIPCHK(hipMemsetAsync(c->fb_cnt, 0, 2 * sizeof(unsigned long long), c->stream));
   const char* trace_path = c->hs.trace_path;

@@ -168,6 +168,22 @@ struct qmfx_ctx {
   qmfx::DevPtr<double> rc_udbl, rc_pscore, rc_scores;
   qmfx::DevPtr<int32_t> rc_pitem, rc_pcnt, rc_counts;
   size_t rc_cap[8] = {};
+  // fold-in (qmfx_wals_fold_in, qmfx_recommend_fold_in): the uploaded foreign rows, their plan
+  // and their own output rows, row losses and status words; scratch grown on demand (fi_cap:
+  // bytes held, in the members' order).  fi_classes / fi_n: the last call's plan.
+  qmfx::DevPtr<int64_t> fi_rowptr;
+  qmfx::DevPtr<int32_t> fi_col;
+  qmfx::DevPtr<void> fi_val, fi_X;
+  qmfx::DevPtr<double> fi_rowloss;
+  qmfx::DevPtr<int32_t> fi_status;
+  qmfx::DevPtr<uint64_t> fi_keys, fi_keys2;
+  qmfx::DevPtr<int64_t> fi_order;
+  qmfx::DevPtr<qmfx::RowDesc> fi_desc;
+  qmfx::DevPtr<int64_t> fi_wb;
+  qmfx::DevPtr<double> fi_out;
+  size_t fi_cap[12] = {};
+  int64_t fi_classes[qmfx::kMaxNTN + 3] = {};
+  int64_t fi_n = -1;  // rows of the last plan (-1: no fold-in yet)
   // similar rows (qmfx_similar, qmfx_factor_norms): one side's row norms, written by every call
   qmfx::DevPtr<double> sim_norms;
   size_t sim_cap = 0;
@@ -366,6 +382,32 @@ hipError_t launch_gram_t(qmfx_ctx* c, const SideBuf& R) {
                                       c->gpart_blocks, c->stream)
                     : launch_gram(R.F.as<T>(), R.n, c->nt, c->G.as<T>(), c->gpart,
                                   c->gpart_blocks, c->stream);
+}
+
+// The fixed side's part of a half, from its current factors: G = YᵀY, and for the whitened
+// rows (use_w) L⁻¹ of G + λI and Z = Y·L⁻ᵀ; G + λI's tile image for the one-wave direct rows.
+template <typename T>
+int fixed_side_prologue(qmfx_ctx* c, const SideBuf& R, double lambda, bool use_w) {
+  // G = YᵀY of the fixed side (full replica on every rank)
+  HIPCHK(launch_gram_t<T>(c, R));
+  if (use_w) {
+    if (c->z_cap < R.n) {
+      // one extra all-zero row (index z_cap): the whitened kernel's padding signals
+      const int64_t cap = std::max(c->s[0].n, c->s[1].n);
+      HIPCHK(dev_alloc(c->Z, (size_t)(cap + 1) * c->kp * c->esz));
+      HIPCHK(hipMemsetAsync(c->Z.as<char>() + (size_t)cap * c->kp * c->esz, 0,
+                            (size_t)c->kp * c->esz, c->stream));
+      c->z_cap = cap;
+    }
+    HIPCHK(hipMemsetAsync(c->chol_status, 0, 4, c->stream));
+    HIPCHK(launch_chol_inv(c->G.as<const T>(), c->nt, c->k, lambda, c->Linv.as<T>(),
+                           c->chol_status, c->chol_scratch, c->stream));
+    HIPCHK(launch_whiten(R.F.as<const T>(), c->Z.as<T>(), nullptr, R.n, c->nt,
+                         c->Linv.as<const T>(), nullptr, 0.0, false, c->cus, c->stream));
+  }
+  if (!use_big_rows(c))
+    HIPCHK(launch_gimg(c->G.as<const T>(), c->nt, c->k, lambda, c->Gimg.as<T>(), c->stream));
+  return 0;
 }
 
 template <typename T>

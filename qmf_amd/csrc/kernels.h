@@ -324,4 +324,29 @@ hipError_t launch_factor_norms(const float* F, int64_t n, int k, int kp, double*
 hipError_t launch_factor_norms(const double* F, int64_t n, int k, int kp, double* norms,
                                hipStream_t s);
 
+// Fold-in (foldin.hip): the row plan of a foreign CSR, built on the device.
+// A row's sort key, low bits first: [row : row_bits][field : n_bits][direct : 1].  Whitened
+// rows (bucket NTN = (max(n, 1) + 15) / 16 ≤ max_ntn) carry field = NTN − 1, direct rows
+// field = max_n − n, so one ascending sort yields the buckets in order with rows ascending
+// inside, then the direct rows by descending n with ties by ascending row: build_buckets'
+// layout for one piece without split-K rows.
+struct FoldKeyBits {
+  int row_bits, n_bits;
+  int end_bit() const { return row_bits + n_bits + 1; }
+};
+FoldKeyBits fold_key_bits(int64_t nrows, int64_t max_n);
+hipError_t launch_fold_keys(const int64_t* rowptr, int64_t nrows, int max_ntn, int64_t max_n,
+                            FoldKeyBits kb, uint64_t* keys, hipStream_t s);
+// sorted keys → order[nrows], desc[nrows] and wb[kMaxNTN + 1]: the first slot of every
+// whitened bucket, wb[kMaxNTN] = the first direct slot
+hipError_t launch_fold_expand(const uint64_t* keys, const int64_t* rowptr, int64_t nrows,
+                              FoldKeyBits kb, int64_t* order, RowDesc* desc, int64_t* wb,
+                              hipStream_t s);
+// out[r·k + f] = X[r·kp + f] widened (the solved rows without their padding columns)
+hipError_t launch_fold_gather(const float* X, int64_t nrows, int k, int kp, double* out,
+                              hipStream_t s);
+hipError_t launch_fold_gather(const double* X, int64_t nrows, int k, int kp, double* out,
+                              hipStream_t s);
+hipError_t launch_iota(int64_t* out, int64_t n, hipStream_t s);  // out[i] = i
+
 }  // namespace qmfx

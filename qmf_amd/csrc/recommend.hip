@@ -299,7 +299,10 @@ __global__ __launch_bounds__(256) void rec_select_kernel(SelArgs<T, Mode> a) {
           const int32_t v = e < end ? a.seen_col[e] : 0;
           const int c = (int)__popcll(__ballot(e < end && (int64_t)v < iend));
           if (c == 0) break;
-          seen = seen || rec_in_window(v, c, item32);
+          // every lane searches (no short circuit): the search reads the window through lane
+          // shuffles, and a lane that skipped it would not supply its entry to the others
+          const bool hit = rec_in_window(v, c, item32);
+          seen = seen || hit;
           cur += c;
           if (c < 64) break;
         }

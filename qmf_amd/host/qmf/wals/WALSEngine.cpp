@@ -1,5 +1,7 @@
 #include <qmf/wals/WALSEngine.h>
 
+#include <algorithm>
+#include <fstream>
 #include <limits>
 #include <random>
 
@@ -200,6 +202,86 @@ void WALSEngine::saveUserSimilarities(const std::string& fileName, const size_t 
                                   const bool cosine, const std::vector<int64_t>* userIds) const {
   CHECK(dev_) << "no factor data, have you initialized the engine?";
   saveSimilarities(dev_->get(), QMFX_USERS, userIndex_, fileName, topN, cosine, userIds);
+}
+
+size_t WALSEngine::foldInUsers(const std::vector<DatasetElem>& lines,
+                               const std::string& userFactorsFile,
+                               const std::string& recommendationsFile, const size_t topN,
+                               const bool includeSeen) const {
+  CHECK(dev_) << "no factor data, have you initialized the engine?";
+  if (!recommendationsFile.empty())
+    CHECK(topN >= 1 && topN <= QMFX_REC_MAX_N)
+        << "the number of recommendations must be in 1.." << QMFX_REC_MAX_N << ", got " << topN;
+  // (user id, item idx, value) of the lines whose item the model knows
+  struct Signal {
+    int64_t user;
+    int32_t item;
+    Double value;
+  };
+  std::vector<Signal> signals;
+  signals.reserve(lines.size());
+  size_t unknown = 0;
+  for (const auto& e : lines) {
+    const size_t i = itemIndex_.idx(e.itemId);
+    if (i == IdIndex::missingIdx)
+      ++unknown;
+    else
+      signals.push_back(Signal{e.userId, static_cast<int32_t>(i), e.value});
+  }
+  if (unknown > 0)
+    LOG(WARNING) << unknown << " fold-in lines name items that are not in the training data; dropped";
+  std::stable_sort(signals.begin(), signals.end(), [](const Signal& a, const Signal& b) {
+    return a.user != b.user ? a.user < b.user : a.item < b.item;
+  });
+  std::vector<int64_t> ids, rowptr(1, 0);
+  std::vector<int32_t> col(signals.size());
+  std::vector<Double> val(signals.size());
+  for (size_t e = 0; e < signals.size(); ++e) {
+    if (e == 0 || signals[e].user != signals[e - 1].user) {
+      if (e > 0) rowptr.push_back(static_cast<int64_t>(e));
+      ids.push_back(signals[e].user);
+    }
+    col[e] = signals[e].item;
+    val[e] = signals[e].value;
+  }
+  if (!signals.empty()) rowptr.push_back(static_cast<int64_t>(signals.size()));
+  const size_t n = ids.size(), k = config_.nfactors;
+  if (n == 0) {
+    LOG(WARNING) << "no fold-in user has a signal on a known item; nothing folded in";
+    if (!userFactorsFile.empty()) std::ofstream(userFactorsFile).flush();
+    if (!recommendationsFile.empty()) std::ofstream(recommendationsFile).flush();
+    return 0;
+  }
+  IdIndex index;
+  index.assignSorted(std::move(ids));
+  FactorData folded(n, k);
+  qmfx_ctx* c = dev_->get();
+  const Double alpha = config_.confidenceWeight, lambda = config_.regularizationLambda;
+  if (recommendationsFile.empty()) {
+    int64_t pivoted = 0;
+    QMFX_CHECK(qmfx_wals_fold_in(c, QMFX_USERS, static_cast<int64_t>(n), rowptr.data(), col.data(),
+                                 val.data(), alpha, lambda, folded.getFactors().data(), nullptr,
+                                 &pivoted));
+    if (pivoted > 0)
+      LOG(WARNING) << pivoted
+                   << " fold-in systems are not positive definite; re-solved with pivoting on the device";
+  } else {
+    std::vector<int64_t> items(n * topN), rows(n);
+    std::vector<double> scores(n * topN);
+    std::vector<int32_t> counts(n);
+    for (size_t r = 0; r < n; ++r) rows[r] = static_cast<int64_t>(r);
+    QMFX_CHECK(qmfx_recommend_fold_in(c, static_cast<int64_t>(n), rowptr.data(), col.data(),
+                                      val.data(), alpha, lambda, static_cast<int>(topN),
+                                      includeSeen ? 0 : 1, items.data(), scores.data(),
+                                      counts.data(), folded.getFactors().data()));
+    std::string text;
+    formatPairs(index, itemIndex_, rows.data(), 0, n, topN, items.data(), scores.data(),
+                counts.data(), text);
+    std::ofstream fout(recommendationsFile);
+    fout.write(text.data(), static_cast<std::streamsize>(text.size()));
+  }
+  if (!userFactorsFile.empty()) saveFactors(folded, index, userFactorsFile);
+  return n;
 }
 
 size_t WALSEngine::nusers() const { return userIndex_.size(); }

@@ -59,6 +59,18 @@ class WALSEngine : public Engine {
   void saveUserSimilarities(const std::string& fileName, size_t topN, bool cosine,
                             const std::vector<int64_t>* userIds = nullptr) const override;
 
+  // Fold-in (addition to the reference API): the users of `lines` are solved as new rows from
+  // these signals against the trained item factors (qmfx_wals_fold_in, rank 0, config's α and
+  // λ), whether or not their id was trained; the model is left as it is.  Lines are grouped by
+  // user id, ascending, with each user's items ascending; a line naming an item that is not in
+  // the training data is dropped, and their number is logged once as a warning.
+  // userFactorsFile (unless empty): "<id> <f0> … <fk-1>" per new user, saveUserFactors' format.
+  // recommendationsFile (unless empty): saveUserRecommendations' format for the new users,
+  // topN per user; includeSeen = false leaves out the items of the user's own lines.
+  // Returns the number of users folded in.
+  size_t foldInUsers(const std::vector<DatasetElem>& lines, const std::string& userFactorsFile,
+                     const std::string& recommendationsFile, size_t topN, bool includeSeen) const;
+
   // --- additions (not in the reference API) ---
   // host copies of the current factors (synchronised from the device on access)
   const FactorData& userFactors() const;

@@ -3,7 +3,12 @@
 // top-N recommendations of the trained model: --user_recommendations, --num_recommendations,
 // --recommend_seen, --recommend_users; and the items' / users' nearest neighbours in factor
 // space: --item_similarities, --user_similarities, --num_similar, --similarity,
-// --similar_item_ids, --similar_user_ids.
+// --similar_item_ids, --similar_user_ids; and fold-in of users the model was not trained on:
+// --fold_in_dataset FILE ("user item weight" lines, the training format; its users are solved
+// as new rows against the trained item factors even if their id was trained, and lines naming
+// an unknown item are dropped with a warning), --fold_in_user_factors OUT (the --user_factors
+// format) and --fold_in_recommendations OUT (the --user_recommendations format, honouring
+// --num_recommendations and --recommend_seen).
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -60,6 +65,12 @@ DEFINE_string(similar_item_ids, "",
 DEFINE_string(similar_user_ids, "",
               "file with one user id per line to list neighbours for (default: every user)");
 
+// fold-in of new users
+DEFINE_string(fold_in_dataset, "", "filename of new users' signals (the training format)");
+DEFINE_string(fold_in_user_factors, "", "filename of the folded-in users' factors");
+DEFINE_string(fold_in_recommendations, "",
+              "filename of the folded-in users' top-N recommendations");
+
 namespace {
 // QMF_TIMINGS=1 (an addition; unset, the output is the reference's): one "timing:" log line per
 // phase with its wall time, read by tools/bench_cli.py
@@ -92,7 +103,10 @@ int main(int argc, char** argv) {
   for (const auto& metric : qmf::split(FLAGS_test_avg_metrics, ',')) {
     CHECK(metricsEngine->addTestAvgMetric(metric)) << "metric " << metric << " is not available";
   }
-  if (!FLAGS_user_recommendations.empty())
+  if (!FLAGS_fold_in_user_factors.empty() || !FLAGS_fold_in_recommendations.empty())
+    CHECK(!FLAGS_fold_in_dataset.empty())
+        << "--fold_in_user_factors and --fold_in_recommendations need --fold_in_dataset";
+  if (!FLAGS_user_recommendations.empty() || !FLAGS_fold_in_recommendations.empty())
     CHECK(FLAGS_num_recommendations >= 1 && FLAGS_num_recommendations <= QMFX_REC_MAX_N)
         << "--num_recommendations must be in 1.." << QMFX_REC_MAX_N;
   CHECK(FLAGS_similarity == "cosine" || FLAGS_similarity == "dot")
@@ -166,6 +180,18 @@ int main(int argc, char** argv) {
     if (timings())
       LOG(INFO) << "timing: similar " << now() - t0 << " s, "
                 << fileBytes(FLAGS_item_similarities) + fileBytes(FLAGS_user_similarities)
+                << " bytes";
+  }
+  if (!FLAGS_fold_in_dataset.empty()) {
+    LOG(INFO) << "folding in new users";
+    t0 = now();
+    qmf::DatasetReader foldReader(FLAGS_fold_in_dataset);
+    const size_t n = engine.foldInUsers(foldReader.readAll(), FLAGS_fold_in_user_factors,
+                                        FLAGS_fold_in_recommendations,
+                                        FLAGS_num_recommendations, FLAGS_recommend_seen);
+    if (timings())
+      LOG(INFO) << "timing: fold_in " << now() - t0 << " s, " << n << " users, "
+                << fileBytes(FLAGS_fold_in_user_factors) + fileBytes(FLAGS_fold_in_recommendations)
                 << " bytes";
   }
   return 0;
