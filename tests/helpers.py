@@ -143,6 +143,78 @@ def ladder_solution(k, seed, precision, alpha, lam, with_empty=True):
     return out
 
 
+# ---- the ladder with negative values, for the pivoted re-solve (tests/test_resolve_gpu.py and
+# its CPU anchor in tests/test_oracle.py)
+SIGNED_RECIPES = ("strong", "mild")
+
+
+@functools.lru_cache(maxsize=None)
+def signed_ladder_case(k, seed, precision, recipe):
+    """ladder_case(k, seed, precision) — the same row lengths, columns, seed and Y — with every
+    signal of index i ≡ 2 (mod 5) within `uval` made negative: "strong" negates it
+    (v ∈ (−5, 0]: most rows of k ≥ 16 become indefinite), "mild" sets it to −0.01·|v|
+    (w = αv ∈ (−2, 0] at α = 40: every system stays SPD).  Both orientations carry the same
+    values; for precision 32 the values are rounded to fp32 after the change.  Cached: the
+    arrays are read-only."""
+    assert recipe in SIGNED_RECIPES, recipe
+    (urp, ucol, v64), (irp, icol, _), _ = ladder_case(k, seed, 64)
+    Y = ladder_case(k, seed, precision)[2]
+    uval = v64.copy()
+    uval[2::5] = -uval[2::5] if recipe == "strong" else -0.01 * np.abs(uval[2::5])
+    if precision == 32:
+        uval = uval.astype(np.float32).astype(np.float64)
+    rows = np.repeat(np.arange(len(urp) - 1), np.diff(urp))
+    order = np.lexsort((rows, ucol))  # by item, then user: ladder_case's item orientation
+    assert np.array_equal(rows[order], icol)
+    ival = uval[order]
+    for a in (uval, ival):
+        a.setflags(write=False)
+    return (urp, ucol, uval), (irp, icol, ival), Y
+
+
+def signed_ladder_reference(rowptr, col, val, Y, alpha, lam):
+    """ladder_reference for systems that need not be positive definite.  Returns
+    (X, loss, cond₂, S, has_neg, lam_min) per row: cond₂ = max|eigenvalue| / min|eigenvalue|
+    of A, has_neg = some weight αv < 0, lam_min = the smallest eigenvalue of A, and
+    S = Σ|c| + |xᵀ(A − λI)x| + 2|xᵀb| (Σc itself may cancel or be negative here; with c ≥ 0 this
+    is ladder_reference's S)."""
+    Y = np.asarray(Y, np.float64)
+    k = Y.shape[1]
+    G = Y.T @ Y
+    nrows = len(rowptr) - 1
+    X = np.zeros((nrows, k))
+    loss, cond, S, lam_min = (np.zeros(nrows) for _ in range(4))
+    has_neg = np.zeros(nrows, bool)
+    for r in range(nrows):
+        sl = slice(int(rowptr[r]), int(rowptr[r + 1]))
+        Yr = Y[col[sl]]
+        w = alpha * np.asarray(val[sl], np.float64)
+        M = G + (Yr.T * w) @ Yr  # A − λI
+        A = M + lam * np.eye(k)
+        b = Yr.T @ (1.0 + w)
+        x = np.linalg.solve(A, b)
+        quad, xb = x @ M @ x, x @ b
+        X[r] = x
+        loss[r] = float(np.sum(1.0 + w)) + quad - 2.0 * xb
+        S[r] = float(np.sum(np.abs(1.0 + w))) + abs(quad) + 2.0 * abs(xb)
+        ev = np.linalg.eigvalsh(A)
+        cond[r] = np.abs(ev).max() / np.abs(ev).min()
+        lam_min[r] = ev[0]
+        has_neg[r] = bool(np.any(w < 0))
+    return X, loss, cond, S, has_neg, lam_min
+
+
+@functools.lru_cache(maxsize=None)
+def signed_ladder_solution(k, seed, precision, recipe, alpha, lam):
+    """signed_ladder_reference of signed_ladder_case(k, seed, precision, recipe)'s user half,
+    computed once per session and shared by the cases on that problem; read-only."""
+    (urp, ucol, uval), _, Y = signed_ladder_case(k, seed, precision, recipe)
+    out = signed_ladder_reference(urp, ucol, uval, Y, alpha, lam)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
 # ---- restatement of the BPR epoch's visiting order and negative draws (qmf_amd/csrc/bpr.hip
 # bpr_epoch_kernel, api_bpr.cpp qmfx_bpr_epoch): counter-based and keyed by positive slot, so
 # the multiset of (u, p, n) of an epoch does not depend on the number of waves

@@ -17,7 +17,7 @@ import pytest
 import pyoracle as po
 from helpers import (LADDER_LENGTHS, bpr_linear_item, bpr_linear_user, bpr_wave_case,
                      bpr_wave_triplets, factor_text, ladder_case, ladder_solution, load_ml100k,
-                     md5)
+                     md5, signed_ladder_case, signed_ladder_solution)
 
 MKL_DIR = "/opt/conda/lib"
 
@@ -217,6 +217,35 @@ def test_ladder_reference_matches_oracle(k):
           % (k, err.max(), abs(lo - loss.sum()) / abs(loss.sum()), cond.max()))
     assert err.max() < 1e-11, (int(np.argmax(err)), err.max())
     assert abs(lo - loss.sum()) <= 1e-11 * abs(loss.sum())
+    assert np.all(S >= np.abs(loss))
+
+
+@pytest.mark.parametrize("k", [16, 33])
+def test_signed_ladder_reference_matches_oracle(k):
+    """Anchors the numpy reference of tests/test_resolve_gpu.py (helpers.signed_ladder_reference)
+    on the CPU: on the strong signed ladder, where most systems are indefinite (dsysv_'s
+    Bunch-Kaufman pivots in the oracle, LU in numpy), the two agree to 1e-9 row by row
+    (‖Δx‖∞ / ‖x‖∞) and in the summed loss.  The oracle builds rows from signals, so the empty
+    row is taken out of the CSRs first."""
+    lam, alpha = 0.05, 40.0
+    (urp, ucol, uval), (irp, icol, ival), Y = signed_ladder_case(k, 1000 + k, 64, "strong")
+    X, loss, cond, S, has_neg, lam_min = signed_ladder_solution(k, 1000 + k, 64, "strong", alpha, lam)
+    assert np.array_equal(uval[2::5] <= 0, np.ones(len(uval[2::5]), bool))
+    assert np.sum(uval < 0) == np.sum(uval[2::5] < 0) and np.sum(lam_min < 0) == {16: 38, 33: 168}[k]
+    assert cond.max() <= 1e6 and np.all(has_neg[lam_min < 0])
+    r0 = int(np.flatnonzero(np.diff(urp) == 0)[0])
+    assert np.all(X[r0] == 0.0) and loss[r0] == 0.0 and not has_neg[r0]
+    keep = np.arange(len(urp) - 1) != r0
+    nu, ni = len(urp) - 2, len(irp) - 1
+    o = po.OracleWALS.from_csr(nu, ni, np.delete(urp, r0), ucol, uval, irp,
+                               (icol - (icol > r0)).astype(np.int32), ival, k, lam, alpha)
+    o.set_factors(1, Y)
+    lo = o.iterate(0) * nu * ni
+    err = np.max(np.abs(o.factors(0) - X[keep]), axis=1) / np.max(np.abs(X[keep]), axis=1)
+    print("k = %d: worst row %.2g, loss %.2g relative, largest cond %.3g, %d indefinite"
+          % (k, err.max(), abs(lo - loss.sum()) / abs(loss.sum()), cond.max(), np.sum(lam_min < 0)))
+    assert err.max() < 1e-9, (int(np.argmax(err)), err.max())
+    assert abs(lo - loss.sum()) <= 1e-9 * np.abs(loss).sum()
     assert np.all(S >= np.abs(loss))
 
 
