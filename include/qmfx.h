@@ -270,6 +270,66 @@ int qmfx_recommend_fold_in(qmfx_ctx* ctx, int64_t nrows, const int64_t* rowptr,
                            double* scores /*nrows·topn*/, int32_t* counts /*nrows*/,
                            double* factors /*NULL or nrows·k*/);
 
+/* ---- explanations: per-signal contributions to a recommendation ------------------------------
+ * WALS is the model of Hu, Koren and Volinsky (2008); with A = G + Σ αv·yyᵀ + λI and
+ * x = A⁻¹ Σ (1+αv)·y the score of a target t splits over the row's own signals:
+ *   y_tᵀx = Σ_e (1+αv_e) · y_tᵀ A⁻¹ y_{j_e}.
+ * For row r of `side`, its signals in CSR order e = 0..n-1 (column j_e = row idx on the other
+ * side, value v_e), w_e = α·v_e, c_e = 1 + α·v_e, and y_j = row j of the other side's factors
+ * as the device holds them, widened to double:
+ *   A         = G + Σ_e w_e·y_{j_e}y_{j_e}ᵀ + λI: exactly what qmfx_wals_row_system(side, r, α, λ)
+ *               returns, G = YᵀY in the context precision, computed by every call, never cached;
+ *   z         = A⁻¹y_t for a target t (row idx on the other side), by a Cholesky factorization of
+ *               A that is kept and reused for all targets of the query;
+ *   contrib_e = c_e · (y_{j_e}·z);  total = Σ_e contrib_e = y_tᵀA⁻¹b = y_t·x̂, x̂ being the row
+ *               qmfx_wals_fold_in returns for these signals.
+ * All arithmetic after G is double, in both context precisions.  Repeated columns are separate
+ * entries with a contribution each.
+ * For a TRAINED row `total` is NOT qmfx_recommend's score: the stored x_u was solved against
+ * the other side's factors of before the last half that changed them.  For a folded-in row
+ * (qmfx_wals_explain_rows with the signals given to qmfx_recommend_fold_in) total is that
+ * score, to rounding.
+ * Selection: entry a ranks before entry b when contrib_a > contrib_b, or they are equal and
+ * a < b by position in the row; the comparison is numeric, as in qmfx_recommend.  Pair p (the
+ * position in targets) gets its first counts[p] = min(topm, n) entries in that order:
+ * sources[p*topm + s] (column idx), positions[p*topm + s] (entry position in the row) and
+ * contribs[p*topm + s]; the unused tail carries -1, -1 and 0.0.  topm is 1..QMFX_REC_MAX_N.
+ * The values in the lists are bit for bit those of `all`, which (when not NULL) receives every
+ * contribution in CSR order, pair after pair: Σ_p n(row of p) doubles.  A row without signals
+ * has count 0 and total exactly 0.0.
+ * Explanations are defined for positive definite systems only: when a query's A has a
+ * non-positive or non-finite Cholesky pivot (some 1 + αv < 0, or λ ≤ 0) the call returns -5 with
+ * a message naming the first such query and fills no output.
+ * qmfx_wals_explain explains rows of the context's own CSR of `side`: query q is row rows[q]
+ * with targets[qptr[q] .. qptr[q+1]) (repeats allowed, an empty list is fine).  On a context
+ * sharded by qmfx_dist_init* it accepts only rows of this rank's row range (the rule of
+ * QMFX_REC_UNSEEN_SIGNALS).  qmfx_wals_explain_rows takes the rows as a CSR of their own
+ * (qmfx_wals_fold_in's rowptr / colidx / values, validated alike): query q is row q; it needs
+ * no CSR on the context and works on any rank.
+ * Fail (-1, with a message, before anything is launched) on: side not 0 or 1, topm out of range,
+ * a row or target out of range, qptr[0] != 0 or qptr decreasing, no factors on the other side,
+ * no CSR of `side` (first form), nfactors > 256.  nq == 0 or no pairs at all succeeds and
+ * touches nothing.  The calls leave the factors, the CSR, the row buckets and what the last
+ * half reported untouched.  Their kernel time (YᵀY included) is counted in
+ * qmfx_solve_kernel_stats with the work  Σ_queries with targets [n·k(k+1) + k³/3]
+ * + Σ_pairs [2k² + 2nk] flop.
+ * The device solves kExplainRhs = 8 targets of a query at a time; the factor lives in LDS up to
+ * 128 (padded) factors and in a context-owned scratch above.
+ * qmfx_row_lengths: the signal counts of rows of the context's CSR (host only; the layout of
+ * `all` for the first form). */
+int qmfx_wals_explain(qmfx_ctx* ctx, int side, int64_t nq, const int64_t* rows,
+                      const int64_t* qptr /*nq+1*/, const int64_t* targets, double alpha,
+                      double lambda, int topm, int64_t* sources /*npairs·topm*/,
+                      int64_t* positions /*npairs·topm*/, double* contribs /*npairs·topm*/,
+                      int32_t* counts /*npairs*/, double* totals /*npairs*/,
+                      double* all /*NULL or Σ_p n(row of p)*/);
+int qmfx_wals_explain_rows(qmfx_ctx* ctx, int side, int64_t nrows, const int64_t* rowptr,
+                           const int32_t* colidx, const double* values, const int64_t* qptr,
+                           const int64_t* targets, double alpha, double lambda, int topm,
+                           int64_t* sources, int64_t* positions, double* contribs,
+                           int32_t* counts, double* totals, double* all);
+int qmfx_row_lengths(qmfx_ctx* ctx, int side, int64_t n, const int64_t* rows, int64_t* lengths);
+
 /* ---- multi-GPU (one process per GPU; RCCL over xGMI) -------------------------------------- */
 int qmfx_rccl_unique_id(uint8_t* id128);
 /* Joins the RCCL communicator (id128 from rank 0's qmfx_rccl_unique_id), takes this rank's
@@ -302,7 +362,8 @@ int qmfx_dist_plan(const int64_t* rowptr, int64_t nrows, int world, int npieces,
 /* HIP-event time of the row-solve kernel launches (on the context stream) since reset; the
  * kernels of qmfx_bpr_epoch, qmfx_recommend and qmfx_similar calls are counted here too (one
  * unit of a similar call is 2k flop per (query, row) pair), and those of the fold-in calls
- * (planning and gather included; the work counted is the k×k form of every row). */
+ * (planning and gather included; the work counted is the k×k form of every row), and those of
+ * the explanation calls (the work formula stands with qmfx_wals_explain). */
 int qmfx_solve_kernel_stats(qmfx_ctx* ctx, double* total_ms, int64_t* launches,
                             double* flops, double* bytes);
 /* Per kernel class since reset: 0 = direct row kernel, 1 = whitened row kernels (row solve

@@ -64,6 +64,11 @@ SIGNATURES = {
     "qmfx_fold_in_order": [vp, P_i64],
     "qmfx_recommend_fold_in": [vp, c_i64, P_i64, P_i32, P_f64, c_dbl, c_dbl, c_int, c_int, P_i64,
                                P_f64, P_i32, P_f64],
+    "qmfx_wals_explain": [vp, c_int, c_i64, P_i64, P_i64, P_i64, c_dbl, c_dbl, c_int, P_i64, P_i64,
+                          P_f64, P_i32, P_f64, P_f64],
+    "qmfx_wals_explain_rows": [vp, c_int, c_i64, P_i64, P_i32, P_f64, P_i64, P_i64, c_dbl, c_dbl,
+                               c_int, P_i64, P_i64, P_f64, P_i32, P_f64, P_f64],
+    "qmfx_row_lengths": [vp, c_int, c_i64, P_i64, P_i64],
     "qmfx_rccl_unique_id": [P_u8],
     "qmfx_dist_init": [vp, c_int, c_int, P_u8],
     "qmfx_partition_rows": [P_i64, c_i64, c_int, c_int, P_i64, P_i64],
@@ -470,6 +475,63 @@ class Context:
                                             int(bool(exclude_seen)), _p(items, P_i64),
                                             _p(scores, P_f64), _p(counts, P_i32), _p(F, P_f64)))
         return items, scores, counts, F
+
+    # ---- explanations
+    def row_lengths(self, side, rows):
+        """The signal counts of rows of the context's CSR of `side`."""
+        rows = np.ascontiguousarray(rows, np.int64)
+        out = np.empty(len(rows), np.int64)
+        _check(lib().qmfx_row_lengths(self.h, int(side), len(rows), _p(rows, P_i64),
+                                      _p(out, P_i64)))
+        return out
+
+    @staticmethod
+    def _explain_out(qptr, targets, lengths, topm, full):
+        """The output arrays of an explain call: lengths[q] = signals of query q's row."""
+        qptr = np.ascontiguousarray(qptr, np.int64)
+        targets = np.ascontiguousarray(targets, np.int64)
+        if len(qptr) != len(lengths) + 1 or (len(qptr) > 1 and qptr[-1] != len(targets)):
+            raise QmfxError("explain query shape mismatch")
+        npairs, w = len(targets), max(int(topm), 0)
+        out = [np.empty((npairs, w), np.int64), np.empty((npairs, w), np.int64),
+               np.empty((npairs, w), np.float64), np.empty(npairs, np.int32),
+               np.empty(npairs, np.float64)]
+        allv = allptr = None
+        if full:
+            per_pair = np.repeat(np.asarray(lengths, np.int64), np.maximum(np.diff(qptr), 0))
+            allptr = np.concatenate([[0], np.cumsum(per_pair)]).astype(np.int64)
+            allv = np.empty(int(allptr[-1]), np.float64)
+        return qptr, targets, out, allv, allptr
+
+    def wals_explain(self, side, rows, qptr, targets, alpha, lam, topm, full=False):
+        """Why is target t recommended to row r?  (sources[np, topm], positions[np, topm],
+        contribs[np, topm], counts[np], totals[np], full) for the pairs (rows[q], t), t in
+        targets[qptr[q]:qptr[q + 1]]: see include/qmfx.h qmfx_wals_explain.  full is None, or
+        with full=True (values, ptr): pair p's contributions in CSR order are
+        values[ptr[p]:ptr[p + 1]].  For a trained row the total is not recommend()'s score (the
+        stored row was solved against older factors of the other side)."""
+        rows = np.ascontiguousarray(rows, np.int64)
+        lengths = self.row_lengths(side, rows) if full else np.zeros(len(rows), np.int64)
+        qptr, targets, out, allv, allptr = self._explain_out(qptr, targets, lengths, topm, full)
+        _check(lib().qmfx_wals_explain(
+            self.h, int(side), len(rows), _p(rows, P_i64), _p(qptr, P_i64), _p(targets, P_i64),
+            float(alpha), float(lam), int(topm), _p(out[0], P_i64), _p(out[1], P_i64),
+            _p(out[2], P_f64), _p(out[3], P_i32), _p(out[4], P_f64),
+            _p(allv, P_f64) if full else None))
+        return (*out, (allv, allptr) if full else None)
+
+    def wals_explain_rows(self, side, rowptr, colidx, values, qptr, targets, alpha, lam, topm,
+                          full=False):
+        """wals_explain for rows given as a CSR of their own (wals_fold_in's): query q is row q.
+        For these rows the total is recommend_fold_in's score, to rounding."""
+        rp, col, val = self._rows(rowptr, colidx, values)
+        qptr, targets, out, allv, allptr = self._explain_out(qptr, targets, np.diff(rp), topm, full)
+        _check(lib().qmfx_wals_explain_rows(
+            self.h, int(side), len(rp) - 1, _p(rp, P_i64), _p(col, P_i32), _p(val, P_f64),
+            _p(qptr, P_i64), _p(targets, P_i64), float(alpha), float(lam), int(topm),
+            _p(out[0], P_i64), _p(out[1], P_i64), _p(out[2], P_f64), _p(out[3], P_i32),
+            _p(out[4], P_f64), _p(allv, P_f64) if full else None))
+        return (*out, (allv, allptr) if full else None)
 
     # ---- dist / stats
     def dist_init(self, rank, world, uid):

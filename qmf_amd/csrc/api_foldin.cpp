@@ -6,12 +6,10 @@
 
 using namespace qmfx;
 
-namespace {
-
-// The one host pass over the new rows: the CSR's shape and every column index (an index out
-// of range would be a device fault).  *max_n: the longest row.
-int validate_rows(int64_t nrows, const int64_t* rowptr, const int32_t* colidx, const double* values,
-                  int64_t nother, bool need_ascending, int64_t* max_n) {
+// The one host pass over the new rows (ctx.h; qmfx_wals_explain_rows validates with it too).
+int qmfx::validate_rows(int64_t nrows, const int64_t* rowptr, const int32_t* colidx,
+                        const double* values, int64_t nother, bool need_ascending,
+                        int64_t* max_n) {
   if (nrows < 0 || nrows > 0x7fffffffll) return fail("nrows out of range (at most 2^31-1 rows)");
   if (!rowptr) return fail("rowptr is null");
   if (rowptr[0] != 0) return fail("rowptr[0] must be 0");
@@ -33,6 +31,8 @@ int validate_rows(int64_t nrows, const int64_t* rowptr, const int32_t* colidx, c
   *max_n = mx;
   return 0;
 }
+
+namespace {
 
 // Uploads the rows, plans them and enqueues their solves (validated input, nrows > 0).
 // Records ev0 in front of the first kernel; leaves the rows in fi_X (padded, context

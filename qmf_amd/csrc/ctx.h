@@ -184,6 +184,17 @@ struct qmfx_ctx {
   size_t fi_cap[12] = {};
   int64_t fi_classes[qmfx::kMaxNTN + 3] = {};
   int64_t fi_n = -1;  // rows of the last plan (-1: no fold-in yet)
+  // explanations (qmfx_wals_explain, qmfx_wals_explain_rows): the uploaded queries (and, for
+  // the rows form, the rows' CSR), the outputs and the KP > 128 factor scratch; grown on demand
+  // (ex_cap: bytes held, in the members' order)
+  qmfx::DevPtr<int64_t> ex_rows, ex_qptr, ex_targets, ex_allq, ex_rowptr;
+  qmfx::DevPtr<int32_t> ex_col;
+  qmfx::DevPtr<void> ex_val;
+  qmfx::DevPtr<int64_t> ex_sources, ex_positions;
+  qmfx::DevPtr<double> ex_contribs, ex_totals, ex_all, ex_scratch;
+  qmfx::DevPtr<int32_t> ex_counts;
+  qmfx::DevPtr<unsigned long long> ex_first;
+  size_t ex_cap[15] = {};
   // similar rows (qmfx_similar, qmfx_factor_norms): one side's row norms, written by every call
   qmfx::DevPtr<double> sim_norms;
   size_t sim_cap = 0;
@@ -441,6 +452,11 @@ void plan_pieces(const std::vector<int64_t>& rp, const std::vector<int64_t>& bou
                  int P, std::vector<int64_t>& pb);
 int build_buckets(qmfx_ctx* c, int side);
 int shard_csr(qmfx_ctx* c, SideBuf& sb);
+
+// api_foldin.cpp: the one host pass over rows given as a CSR of their own: the CSR's shape and
+// every column index (an index out of range would be a device fault).  *max_n: the longest row.
+int validate_rows(int64_t nrows, const int64_t* rowptr, const int32_t* colidx, const double* values,
+                  int64_t nother, bool need_ascending, int64_t* max_n);
 
 // api_eval.cpp
 void drop_eval_labels(qmfx_ctx* c);  // releases the test-label set (qmfx_eval_ranks then fails)

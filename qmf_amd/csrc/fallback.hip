@@ -16,13 +16,11 @@
 // time through LDS.
 #include "common.h"
 #include "kernels.h"
+#include "system.h"
 
 namespace qmfx {
 
 namespace {
-
-constexpr int FB_THREADS = 256;
-constexpr int FB_CHUNK = 16;
 
 __device__ double block_argmax_abs(const double* A, int KP, int j, int tid, double* red_v,
                                    int* red_i, int& piv) {
@@ -54,53 +52,6 @@ __device__ double block_argmax_abs(const double* A, int KP, int j, int tid, doub
   const double r = red_v[0];
   __syncthreads();
   return r;
-}
-
-// Builds A (KP×KP, row-major; padding diagonal 1), b and Σc of `row` into scratch.
-template <typename T>
-__device__ void build_system(const FallbackArgs<T>& a, int64_t beg, int64_t end, double* A,
-                             double* b, double& csum, double (*ys)[256], double* ws,
-                             double* cs, int tid) {
-  const int KP = a.kp, k = a.k;
-  for (int idx = tid; idx < KP * KP; idx += FB_THREADS) {
-    const int i = idx / KP, j = idx % KP;
-    double v = (i < k && j < k) ? (double)a.G[idx] : 0.0;
-    if (i == j) v += i < k ? (double)a.lambda : 1.0;
-    A[idx] = v;
-  }
-  for (int i = tid; i < KP; i += FB_THREADS) b[i] = 0.0;
-  double cacc = 0.0;
-  __syncthreads();
-  for (int64_t base = beg; base < end; base += FB_CHUNK) {
-    const int m = (int)(end - base < FB_CHUNK ? end - base : FB_CHUNK);
-    for (int idx = tid; idx < FB_CHUNK * KP; idx += FB_THREADS) {
-      const int e = idx / KP, j = idx % KP;
-      ys[e][j] = (e < m && j < k) ? (double)a.Y[(size_t)(uint32_t)a.col[base + e] * KP + j] : 0.0;
-    }
-    if (tid < FB_CHUNK) {
-      const double v = tid < m ? (double)a.val[base + tid] : 0.0;
-      ws[tid] = tid < m ? (double)a.alpha * v : 0.0;
-      cs[tid] = tid < m ? 1.0 + (double)a.alpha * v : 0.0;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < KP * KP; idx += FB_THREADS) {
-      const int i = idx / KP, j = idx % KP;
-      double s = 0.0;
-#pragma unroll
-      for (int e = 0; e < FB_CHUNK; ++e) s += ws[e] * ys[e][i] * ys[e][j];
-      A[idx] += s;
-    }
-    for (int i = tid; i < KP; i += FB_THREADS) {
-      double s = 0.0;
-#pragma unroll
-      for (int e = 0; e < FB_CHUNK; ++e) s += cs[e] * ys[e][i];
-      b[i] += s;
-    }
-    if (tid == 0)
-      for (int e = 0; e < m; ++e) cacc += cs[e];
-    __syncthreads();
-  }
-  csum = cacc;  // valid on thread 0
 }
 
 }  // namespace
@@ -135,7 +86,7 @@ __global__ __launch_bounds__(FB_THREADS) void wals_fallback_kernel(FallbackArgs<
     for (int li = 0; li < cnt; ++li) {
       const RowDesc d = a.desc[base + list[li]];
       double csum = 0.0;
-      build_system<T>(a, d.beg, d.beg + d.n, A, b, csum, ys, ws, cs, tid);
+      build_system<T, 256, false>(a, d.beg, d.beg + d.n, A, b, csum, ys, ws, cs, tid);
       for (int i = tid; i < KP; i += FB_THREADS) b0[i] = b[i];
       if (tid == 0) sing = 0;
       __syncthreads();
@@ -227,7 +178,7 @@ __global__ __launch_bounds__(FB_THREADS) void wals_system_kernel(FallbackArgs<T>
   double* A = a.scratch;
   double* b = A + (size_t)KP * KP;
   double csum = 0.0;
-  build_system<T>(a, beg, end, A, b, csum, ys, ws, cs, tid);
+  build_system<T, 256, false>(a, beg, end, A, b, csum, ys, ws, cs, tid);
   __syncthreads();
   for (int idx = tid; idx < k * k; idx += FB_THREADS)
     out[idx] = A[(size_t)(idx / k) * KP + idx % k];

@@ -349,4 +349,32 @@ hipError_t launch_fold_gather(const double* X, int64_t nrows, int k, int kp, dou
                               hipStream_t s);
 hipError_t launch_iota(int64_t* out, int64_t n, hipStream_t s);  // out[i] = i
 
+// Explanations (explain.hip): per-signal contributions c_e·y_eᵀA⁻¹y_t to a row's score of a
+// target, from one kept Cholesky factor of the row's system per query.
+constexpr int kExplainRhs = 8;          // right-hand sides (targets) solved together
+constexpr int kExplainLdsMaxKP = 128;   // the packed factor lives in LDS up to this KP
+template <typename T>
+struct ExplainArgs {
+  // of sys: col, val (indexed with rowptr's offsets), Y, G, alpha, lambda, k, kp; scratch: one
+  // packed triangle KP(KP+1)/2 per workgroup when KP > kExplainLdsMaxKP
+  FallbackArgs<T> sys;
+  const int64_t* rowptr;   // CSR of the explained rows
+  const int64_t* rows;     // [nq] row of query q, or nullptr: query q is row q
+  int64_t nq;
+  const int64_t* qptr;     // [nq + 1] query q explains targets[qptr[q] .. qptr[q + 1])
+  const int64_t* targets;  // row indices of Y
+  int topm;                // 1..kRecMaxN
+  int64_t* sources;        // [npairs][topm] column of the signal, −1 in the unused tail
+  int64_t* positions;      // [npairs][topm] its position in the row, −1 in the tail
+  double* contribs;        // [npairs][topm] 0.0 in the tail
+  int32_t* counts;         // [npairs] min(topm, n)
+  double* totals;          // [npairs]
+  double* all;             // nullptr, or every contribution: query q's pairs from allq[q], n each
+  const int64_t* allq;     // [nq]
+  unsigned long long* first_bad;  // the smallest query whose system is not positive definite
+};
+int explain_grid(int64_t nq, int kp);
+hipError_t launch_explain(const ExplainArgs<float>& a, hipStream_t s);
+hipError_t launch_explain(const ExplainArgs<double>& a, hipStream_t s);
+
 }  // namespace qmfx

@@ -206,6 +206,50 @@ void Engine::formatPairs(const IdIndex& queryIndex, const IdIndex& otherIndex,
   }
 }
 
+void Engine::formatExplanations(const IdIndex& queryIndex, const IdIndex& otherIndex,
+                                const int64_t* pairRows, const int64_t* targets, const size_t b,
+                                const size_t e, const size_t topM, const int64_t* sources,
+                                const double* contribs, const int32_t* counts, std::string& s) {
+  char buf[32];
+  for (size_t p = b; p < e; ++p) {
+    std::string head;
+    head.append(buf, std::to_chars(buf, buf + sizeof(buf), static_cast<long long>(queryIndex.id(
+                                                               static_cast<size_t>(pairRows[p])))).ptr);
+    head.push_back(' ');
+    head.append(buf, std::to_chars(buf, buf + sizeof(buf), static_cast<long long>(otherIndex.id(
+                                                               static_cast<size_t>(targets[p])))).ptr);
+    head.push_back(' ');
+    for (int32_t r = 0; r < counts[p]; ++r) {
+      s += head;
+      const size_t src = static_cast<size_t>(sources[p * topM + r]);
+      s.append(buf, std::to_chars(buf, buf + sizeof(buf),
+                                  static_cast<long long>(otherIndex.id(src))).ptr);
+      appendFixed9(s, contribs[p * topM + r]);
+      s.push_back('\n');
+    }
+  }
+}
+
+void Engine::writeExplanations(const IdIndex& queryIndex, const IdIndex& otherIndex,
+                               const std::vector<int64_t>& pairRows,
+                               const std::vector<int64_t>& targets, const size_t topM,
+                               const int64_t* sources, const double* contribs,
+                               const int32_t* counts, std::ostream& out) {
+  const size_t n = targets.size(), block = 4096, nblocks = (n + block - 1) / block;
+  const unsigned hc = std::thread::hardware_concurrency();
+  const size_t nt = std::max<size_t>(1, std::min<size_t>(hc ? hc : 1, 16));
+  for (size_t b0 = 0; b0 < nblocks; b0 += nt) {
+    const size_t nb = std::min(nt, nblocks - b0);
+    std::vector<std::string> parts(nb);
+    ParallelExecutor::run(nb, [&](const size_t p) {
+      const size_t b = (b0 + p) * block, e = std::min(n, b + block);
+      formatExplanations(queryIndex, otherIndex, pairRows.data(), targets.data(), b, e, topM,
+                         sources, contribs, counts, parts[p]);
+    });
+    for (const auto& p : parts) out.write(p.data(), static_cast<std::streamsize>(p.size()));
+  }
+}
+
 namespace {
 
 // The batches of a save call: `select` fills one batch's lists (n queries from rows + r0),
@@ -213,7 +257,7 @@ namespace {
 template <typename Select>
 void savePairs(const IdIndex& queryIndex, const IdIndex& otherIndex,
                const std::vector<int64_t>& rows, const std::string& fileName, const size_t topN,
-               const Select& select) {
+               const Select& select, const Engine::AfterBatch* after = nullptr) {
   std::ofstream fout(fileName);
   const size_t batch = 65536, block = 4096;
   const unsigned hc = std::thread::hardware_concurrency();
@@ -224,6 +268,7 @@ void savePairs(const IdIndex& queryIndex, const IdIndex& otherIndex,
   for (size_t r0 = 0; r0 < rows.size(); r0 += batch) {
     const size_t n = std::min(batch, rows.size() - r0);
     select(rows.data() + r0, n, others.data(), scores.data(), counts.data());
+    if (after) (*after)(rows.data() + r0, n, others.data(), counts.data());
     const size_t nblocks = (n + block - 1) / block;
     for (size_t b0 = 0; b0 < nblocks; b0 += nt) {
       const size_t nb = std::min(nt, nblocks - b0);
@@ -243,7 +288,7 @@ void savePairs(const IdIndex& queryIndex, const IdIndex& otherIndex,
 void Engine::saveRecommendations(qmfx_ctx* ctx, const int exclude, const bool useBiases,
                                  const IdIndex& userIndex, const IdIndex& itemIndex,
                                  const std::string& fileName, const size_t topN,
-                                 const std::vector<int64_t>* userIds) {
+                                 const std::vector<int64_t>* userIds, const AfterBatch* after) {
   CHECK(topN >= 1 && topN <= QMFX_REC_MAX_N)
       << "the number of recommendations must be in 1.." << QMFX_REC_MAX_N << ", got " << topN;
   const std::vector<int64_t> users = queryRows(userIndex, userIds, "user");
@@ -253,7 +298,8 @@ void Engine::saveRecommendations(qmfx_ctx* ctx, const int exclude, const bool us
               QMFX_CHECK(qmfx_recommend(ctx, static_cast<int64_t>(n), rows,
                                         static_cast<int>(topN), exclude, useBiases ? 1 : 0,
                                         items, scores, counts));
-            });
+            },
+            after);
 }
 
 void Engine::saveSimilarities(qmfx_ctx* ctx, const int side, const IdIndex& index,

@@ -2,6 +2,7 @@
 // Non-copyable, non-movable; errors abort through CHECK as in the reference.
 #pragma once
 
+#include <functional>
 #include <ostream>
 #include <string>
 #include <vector>
@@ -66,13 +67,34 @@ class Engine {
                           const int64_t* others, const double* scores, const int32_t* counts,
                           std::string& s);
 
+  // Appends "<queryId> <targetId> <sourceId> <contribution>\n" (%.9f) for pairs [b, e): pair p
+  // is query idx pairRows[p] of queryIndex and target idx targets[p] of otherIndex, explained
+  // by sources[p·topM + s] (idx of otherIndex) with contribs[p·topM + s] for s < counts[p].
+  static void formatExplanations(const IdIndex& queryIndex, const IdIndex& otherIndex,
+                                 const int64_t* pairRows, const int64_t* targets, size_t b,
+                                 size_t e, size_t topM, const int64_t* sources,
+                                 const double* contribs, const int32_t* counts, std::string& s);
+
+  // called after a batch of a save call has been selected: its n query rows and their lists
+  using AfterBatch = std::function<void(const int64_t* rows, size_t n, const int64_t* others,
+                                        const int32_t* counts)>;
+
  protected:
   // saveUserRecommendations of the engines: qmfx_recommend (include/qmfx.h) with the given
-  // exclude mode in batches of at most 65,536 users, formatted and written batch by batch
+  // exclude mode in batches of at most 65,536 users, formatted and written batch by batch;
+  // `after` (unless null) sees every batch's lists once they are selected
   static void saveRecommendations(qmfx_ctx* ctx, int exclude, bool useBiases,
                                   const IdIndex& userIndex, const IdIndex& itemIndex,
                                   const std::string& fileName, size_t topN,
-                                  const std::vector<int64_t>* userIds);
+                                  const std::vector<int64_t>* userIds,
+                                  const AfterBatch* after = nullptr);
+
+  // formatExplanations of all the pairs, in blocks in parallel, written to `out` in order
+  static void writeExplanations(const IdIndex& queryIndex, const IdIndex& otherIndex,
+                                const std::vector<int64_t>& pairRows,
+                                const std::vector<int64_t>& targets, size_t topM,
+                                const int64_t* sources, const double* contribs,
+                                const int32_t* counts, std::ostream& out);
 
   // save{Item,User}Similarities of the engines: qmfx_similar on `side` (whose id table is
   // `index`) in batches of at most 65,536 queries, written batch by batch

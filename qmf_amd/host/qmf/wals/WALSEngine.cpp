@@ -192,6 +192,65 @@ void WALSEngine::saveUserRecommendations(const std::string& fileName, const size
                       userIndex_, itemIndex_, fileName, topN, userIds);
 }
 
+namespace {
+
+// the (user, item) pairs of a batch's recommendation lists as explain queries: query t
+// explains targets[qptr[t] .. qptr[t + 1]); pairRows[p] = rows[t] of pair p's query
+void listsToQueries(const int64_t* rows, const size_t n, const size_t topN, const int64_t* items,
+                    const int32_t* counts, std::vector<int64_t>& qptr,
+                    std::vector<int64_t>& targets, std::vector<int64_t>& pairRows) {
+  qptr.assign(n + 1, 0);
+  targets.clear();
+  pairRows.clear();
+  for (size_t t = 0; t < n; ++t) {
+    for (int32_t r = 0; r < counts[t]; ++r) {
+      targets.push_back(items[t * topN + static_cast<size_t>(r)]);
+      pairRows.push_back(rows[t]);
+    }
+    qptr[t + 1] = static_cast<int64_t>(targets.size());
+  }
+}
+
+struct ExplainLists {
+  std::vector<int64_t> sources, positions;
+  std::vector<double> contribs, totals;
+  std::vector<int32_t> counts;
+  ExplainLists(const size_t npairs, const size_t topM)
+      : sources(npairs * topM), positions(npairs * topM), contribs(npairs * topM),
+        totals(npairs), counts(npairs) {}
+};
+
+}  // namespace
+
+void WALSEngine::saveRecommendationExplanations(const std::string& recommendationsFile,
+                                                const std::string& explanationsFile,
+                                                const size_t topN, const size_t topM,
+                                                const bool includeSeen,
+                                                const std::vector<int64_t>* userIds) const {
+  CHECK(dev_) << "no factor data, have you initialized the engine?";
+  CHECK_EQ(ranks_.size(), 1u) << "recommendations need --ngpus=1";
+  CHECK(topM >= 1 && topM <= QMFX_REC_MAX_N)
+      << "the number of explanations must be in 1.." << QMFX_REC_MAX_N << ", got " << topM;
+  qmfx_ctx* c = dev_->get();
+  const Double alpha = config_.confidenceWeight, lambda = config_.regularizationLambda;
+  std::ofstream eout(explanationsFile);
+  std::vector<int64_t> qptr, targets, pairRows;
+  const AfterBatch after = [&](const int64_t* rows, const size_t n, const int64_t* items,
+                               const int32_t* counts) {
+    listsToQueries(rows, n, topN, items, counts, qptr, targets, pairRows);
+    if (targets.empty()) return;
+    ExplainLists x(targets.size(), topM);
+    QMFX_CHECK(qmfx_wals_explain(c, QMFX_USERS, static_cast<int64_t>(n), rows, qptr.data(),
+                                 targets.data(), alpha, lambda, static_cast<int>(topM),
+                                 x.sources.data(), x.positions.data(), x.contribs.data(),
+                                 x.counts.data(), x.totals.data(), nullptr));
+    writeExplanations(userIndex_, itemIndex_, pairRows, targets, topM, x.sources.data(),
+                      x.contribs.data(), x.counts.data(), eout);
+  };
+  saveRecommendations(c, includeSeen ? QMFX_REC_ALL : QMFX_REC_UNSEEN_SIGNALS, false, userIndex_,
+                      itemIndex_, recommendationsFile, topN, userIds, &after);
+}
+
 void WALSEngine::saveItemSimilarities(const std::string& fileName, const size_t topN,
                                   const bool cosine, const std::vector<int64_t>* itemIds) const {
   CHECK(dev_) << "no factor data, have you initialized the engine?";
@@ -207,8 +266,14 @@ void WALSEngine::saveUserSimilarities(const std::string& fileName, const size_t 
 size_t WALSEngine::foldInUsers(const std::vector<DatasetElem>& lines,
                                const std::string& userFactorsFile,
                                const std::string& recommendationsFile, const size_t topN,
-                               const bool includeSeen) const {
+                               const bool includeSeen, const std::string& explanationsFile,
+                               const size_t topM) const {
   CHECK(dev_) << "no factor data, have you initialized the engine?";
+  if (!explanationsFile.empty()) {
+    CHECK(!recommendationsFile.empty()) << "fold-in explanations need the recommendations file";
+    CHECK(topM >= 1 && topM <= QMFX_REC_MAX_N)
+        << "the number of explanations must be in 1.." << QMFX_REC_MAX_N << ", got " << topM;
+  }
   if (!recommendationsFile.empty())
     CHECK(topN >= 1 && topN <= QMFX_REC_MAX_N)
         << "the number of recommendations must be in 1.." << QMFX_REC_MAX_N << ", got " << topN;
@@ -250,6 +315,7 @@ size_t WALSEngine::foldInUsers(const std::vector<DatasetElem>& lines,
     LOG(WARNING) << "no fold-in user has a signal on a known item; nothing folded in";
     if (!userFactorsFile.empty()) std::ofstream(userFactorsFile).flush();
     if (!recommendationsFile.empty()) std::ofstream(recommendationsFile).flush();
+    if (!explanationsFile.empty()) std::ofstream(explanationsFile).flush();
     return 0;
   }
   IdIndex index;
@@ -279,6 +345,21 @@ size_t WALSEngine::foldInUsers(const std::vector<DatasetElem>& lines,
                 counts.data(), text);
     std::ofstream fout(recommendationsFile);
     fout.write(text.data(), static_cast<std::streamsize>(text.size()));
+    if (!explanationsFile.empty()) {
+      std::ofstream eout(explanationsFile);
+      std::vector<int64_t> qptr, targets, pairRows;
+      listsToQueries(rows.data(), n, topN, items.data(), counts.data(), qptr, targets, pairRows);
+      if (!targets.empty()) {
+        ExplainLists x(targets.size(), topM);
+        QMFX_CHECK(qmfx_wals_explain_rows(c, QMFX_USERS, static_cast<int64_t>(n), rowptr.data(),
+                                          col.data(), val.data(), qptr.data(), targets.data(),
+                                          alpha, lambda, static_cast<int>(topM), x.sources.data(),
+                                          x.positions.data(), x.contribs.data(), x.counts.data(),
+                                          x.totals.data(), nullptr));
+        writeExplanations(index, itemIndex_, pairRows, targets, topM, x.sources.data(),
+                          x.contribs.data(), x.counts.data(), eout);
+      }
+    }
   }
   if (!userFactorsFile.empty()) saveFactors(folded, index, userFactorsFile);
   return n;

@@ -53,6 +53,18 @@ class WALSEngine : public Engine {
   // includeSeen = false leaves out the items of the user's training signals (one GPU only)
   void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
                                const std::vector<int64_t>* userIds = nullptr) const override;
+  // saveUserRecommendations to recommendationsFile, and to explanationsFile why: for every
+  // (user, item) pair of that file, in its order, the topM (1..QMFX_REC_MAX_N) training signals
+  // of the user that contribute most to y_itemᵀA_u⁻¹b_u (include/qmfx.h qmfx_wals_explain, the
+  // config's α and λ), one line "<userId> <itemId> <sourceItemId> <contribution>\n" (%.9f) per
+  // source, in rank order.  The contributions of a pair add up to the score of the user solved
+  // from the current item factors, which is not the recommendation's score (the stored user
+  // row was solved before the last item half).  Needs positive definite systems: the device
+  // refuses (and this aborts) when a user has a signal with 1 + αv < 0.  One GPU only.
+  void saveRecommendationExplanations(const std::string& recommendationsFile,
+                                      const std::string& explanationsFile, size_t topN,
+                                      size_t topM, bool includeSeen,
+                                      const std::vector<int64_t>* userIds = nullptr) const;
   // the query itself is always left out; with several GPUs rank 0 answers (full replicas)
   void saveItemSimilarities(const std::string& fileName, size_t topN, bool cosine,
                             const std::vector<int64_t>* itemIds = nullptr) const override;
@@ -67,9 +79,13 @@ class WALSEngine : public Engine {
   // userFactorsFile (unless empty): "<id> <f0> … <fk-1>" per new user, saveUserFactors' format.
   // recommendationsFile (unless empty): saveUserRecommendations' format for the new users,
   // topN per user; includeSeen = false leaves out the items of the user's own lines.
+  // explanationsFile (unless empty; needs recommendationsFile): saveRecommendationExplanations'
+  // format for the pairs of recommendationsFile, topM sources per pair, from the new users' own
+  // lines (qmfx_wals_explain_rows); here a pair's contributions add up to its score.
   // Returns the number of users folded in.
   size_t foldInUsers(const std::vector<DatasetElem>& lines, const std::string& userFactorsFile,
-                     const std::string& recommendationsFile, size_t topN, bool includeSeen) const;
+                     const std::string& recommendationsFile, size_t topN, bool includeSeen,
+                     const std::string& explanationsFile = "", size_t topM = 5) const;
 
   // --- additions (not in the reference API) ---
   // host copies of the current factors (synchronised from the device on access)

@@ -8,7 +8,13 @@
 // as new rows against the trained item factors even if their id was trained, and lines naming
 // an unknown item are dropped with a warning), --fold_in_user_factors OUT (the --user_factors
 // format) and --fold_in_recommendations OUT (the --user_recommendations format, honouring
-// --num_recommendations and --recommend_seen).
+// --num_recommendations and --recommend_seen); and why an item is recommended:
+// --recommendation_explanations OUT (needs --user_recommendations) and --fold_in_explanations OUT
+// (needs --fold_in_recommendations): for every (user, item) pair of the recommendations file,
+// in its order, one line "<userId> <itemId> <sourceItemId> <contribution>" per source, the
+// --num_explanations (default 5, 1..128) signals of the user that contribute most, in rank
+// order.  A pair's contributions add up to the score of the user solved from the final item
+// factors: the recommendation's score for a folded-in user, not for a trained one.
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -70,6 +76,12 @@ DEFINE_string(fold_in_dataset, "", "filename of new users' signals (the training
 DEFINE_string(fold_in_user_factors, "", "filename of the folded-in users' factors");
 DEFINE_string(fold_in_recommendations, "",
               "filename of the folded-in users' top-N recommendations");
+// explanations
+DEFINE_string(recommendation_explanations, "",
+              "filename of the per-signal contributions to the pairs of --user_recommendations");
+DEFINE_string(fold_in_explanations, "",
+              "filename of the per-signal contributions to the pairs of --fold_in_recommendations");
+DEFINE_uint64(num_explanations, 5, "sources listed per recommended pair (1..128)");
 
 namespace {
 // QMF_TIMINGS=1 (an addition; unset, the output is the reference's): one "timing:" log line per
@@ -109,6 +121,15 @@ int main(int argc, char** argv) {
   if (!FLAGS_user_recommendations.empty() || !FLAGS_fold_in_recommendations.empty())
     CHECK(FLAGS_num_recommendations >= 1 && FLAGS_num_recommendations <= QMFX_REC_MAX_N)
         << "--num_recommendations must be in 1.." << QMFX_REC_MAX_N;
+  if (!FLAGS_recommendation_explanations.empty())
+    CHECK(!FLAGS_user_recommendations.empty())
+        << "--recommendation_explanations needs --user_recommendations";
+  if (!FLAGS_fold_in_explanations.empty())
+    CHECK(!FLAGS_fold_in_recommendations.empty())
+        << "--fold_in_explanations needs --fold_in_recommendations";
+  if (!FLAGS_recommendation_explanations.empty() || !FLAGS_fold_in_explanations.empty())
+    CHECK(FLAGS_num_explanations >= 1 && FLAGS_num_explanations <= QMFX_REC_MAX_N)
+        << "--num_explanations must be in 1.." << QMFX_REC_MAX_N;
   CHECK(FLAGS_similarity == "cosine" || FLAGS_similarity == "dot")
       << "--similarity must be cosine or dot";
   if (!FLAGS_item_similarities.empty() || !FLAGS_user_similarities.empty())
@@ -155,9 +176,14 @@ int main(int argc, char** argv) {
     t0 = now();
     std::vector<int64_t> ids;
     if (!FLAGS_recommend_users.empty()) ids = qmf::readIds(FLAGS_recommend_users);
-    engine.saveUserRecommendations(FLAGS_user_recommendations, FLAGS_num_recommendations,
-                                   FLAGS_recommend_seen,
-                                   FLAGS_recommend_users.empty() ? nullptr : &ids);
+    const std::vector<int64_t>* users = FLAGS_recommend_users.empty() ? nullptr : &ids;
+    if (FLAGS_recommendation_explanations.empty())
+      engine.saveUserRecommendations(FLAGS_user_recommendations, FLAGS_num_recommendations,
+                                     FLAGS_recommend_seen, users);
+    else
+      engine.saveRecommendationExplanations(
+          FLAGS_user_recommendations, FLAGS_recommendation_explanations,
+          FLAGS_num_recommendations, FLAGS_num_explanations, FLAGS_recommend_seen, users);
     if (timings())
       LOG(INFO) << "timing: recommend " << now() - t0 << " s, "
                 << fileBytes(FLAGS_user_recommendations) << " bytes";
@@ -188,7 +214,8 @@ int main(int argc, char** argv) {
     qmf::DatasetReader foldReader(FLAGS_fold_in_dataset);
     const size_t n = engine.foldInUsers(foldReader.readAll(), FLAGS_fold_in_user_factors,
                                         FLAGS_fold_in_recommendations,
-                                        FLAGS_num_recommendations, FLAGS_recommend_seen);
+                                        FLAGS_num_recommendations, FLAGS_recommend_seen,
+                                        FLAGS_fold_in_explanations, FLAGS_num_explanations);
     if (timings())
       LOG(INFO) << "timing: fold_in " << now() - t0 << " s, " << n << " users, "
                 << fileBytes(FLAGS_fold_in_user_factors) + fileBytes(FLAGS_fold_in_recommendations)
