@@ -113,8 +113,8 @@ int qmfx_set_shape(qmfx_ctx* c, int64_t nusers, int64_t nitems) {
     }
   }
   // What was sized or indexed by the old row counts goes with them; a call that needs it
-  // fails until it is set again (scratch behind a capacity check, such as rowloss, Z and the
-  // rc_* buffers, regrows on demand and stays).
+  // fails until it is set again (scratch behind a capacity check, such as rowloss, Z and
+  // every Scratch buffer, regrows on demand and stays).
   if (users_changed || items_changed) {
     drop_eval_labels(c);
     drop_bpr_positives(c);

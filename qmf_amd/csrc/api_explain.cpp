@@ -1,7 +1,7 @@
 // Explanations: the per-signal contributions to y_tᵀA⁻¹b of a row's system, for rows of the
 // context's own CSR (qmfx_wals_explain) or rows given as a CSR of their own
 // (qmfx_wals_explain_rows).  One kernel (explain.hip) after the fixed side's YᵀY.
-#include "ctx.h"
+#include "rows.h"
 
 using namespace qmfx;
 
@@ -67,22 +67,22 @@ int explain_run(qmfx_ctx* c, int side, int64_t nq, const int64_t* rows, const in
   const bool in_lds = c->kp <= kExplainLdsMaxKP;
   const size_t tri = (size_t)c->kp * (c->kp + 1) / 2;
   if (rows)
-    if (int rc = grow(c->ex_rows, c->ex_cap[0], nq1 * 8)) return rc;
-  if (int rc = grow(c->ex_qptr, c->ex_cap[1], (nq1 + 1) * 8)) return rc;
-  if (int rc = grow(c->ex_targets, c->ex_cap[2], np * 8)) return rc;
+    if (int rc = reserve(c->ex_rows, nq1 * 8)) return rc;
+  if (int rc = reserve(c->ex_qptr, (nq1 + 1) * 8)) return rc;
+  if (int rc = reserve(c->ex_targets, np * 8)) return rc;
   if (o.all)
-    if (int rc = grow(c->ex_allq, c->ex_cap[3], nq1 * 8)) return rc;
-  if (int rc = grow(c->ex_sources, c->ex_cap[7], lists * 8)) return rc;
-  if (int rc = grow(c->ex_positions, c->ex_cap[8], lists * 8)) return rc;
-  if (int rc = grow(c->ex_contribs, c->ex_cap[9], lists * 8)) return rc;
-  if (int rc = grow(c->ex_totals, c->ex_cap[10], np * 8)) return rc;
+    if (int rc = reserve(c->ex_allq, nq1 * 8)) return rc;
+  if (int rc = reserve(c->ex_sources, lists * 8)) return rc;
+  if (int rc = reserve(c->ex_positions, lists * 8)) return rc;
+  if (int rc = reserve(c->ex_contribs, lists * 8)) return rc;
+  if (int rc = reserve(c->ex_totals, np * 8)) return rc;
   if (o.all && nall > 0)
-    if (int rc = grow(c->ex_all, c->ex_cap[11], (size_t)nall * 8)) return rc;
+    if (int rc = reserve(c->ex_all, (size_t)nall * 8)) return rc;
   if (!in_lds)
-    if (int rc = grow(c->ex_scratch, c->ex_cap[12], (size_t)explain_grid(nq, c->kp) * tri * 8))
+    if (int rc = reserve(c->ex_scratch, (size_t)explain_grid(nq, c->kp) * tri * 8))
       return rc;
-  if (int rc = grow(c->ex_counts, c->ex_cap[13], np * 4)) return rc;
-  if (int rc = grow(c->ex_first, c->ex_cap[14], 8)) return rc;
+  if (int rc = reserve(c->ex_counts, np * 4)) return rc;
+  if (int rc = reserve(c->ex_first, 8)) return rc;
   if (rows) HIPCHK(scopy(c, c->ex_rows, rows, nq1 * 8, hipMemcpyHostToDevice));
   HIPCHK(scopy(c, c->ex_qptr, qptr, (nq1 + 1) * 8, hipMemcpyHostToDevice));
   HIPCHK(scopy(c, c->ex_targets, targets, np * 8, hipMemcpyHostToDevice));
@@ -184,16 +184,8 @@ int qmfx_wals_explain_rows(qmfx_ctx* c, int side, int64_t nrows, const int64_t* 
     return rc;
   if (npairs == 0) return 0;
   if (set_dev(c)) return -2;
-  const size_t n1 = (size_t)nrows, nnz = (size_t)rowptr[nrows], m1 = std::max<size_t>(nnz, 1);
-  if (int rc = grow(c->ex_rowptr, c->ex_cap[4], (n1 + 1) * 8)) return rc;
-  if (int rc = grow(c->ex_col, c->ex_cap[5], m1 * 4)) return rc;
-  if (int rc = grow(c->ex_val, c->ex_cap[6], m1 * c->esz)) return rc;
-  HIPCHK(scopy(c, c->ex_rowptr, rowptr, (n1 + 1) * 8, hipMemcpyHostToDevice));
-  if (nnz > 0) {
-    HIPCHK(scopy(c, c->ex_col, colidx, nnz * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_in(c, c->ex_val, values, nnz));
-  }
-  return explain_run(c, side, nrows, nullptr, rowptr, c->ex_rowptr, c->ex_col, c->ex_val, qptr,
+  if (int rc = upload_rows(c, nrows, rowptr, colidx, values)) return rc;
+  return explain_run(c, side, nrows, nullptr, rowptr, c->fr_rowptr, c->fr_col, c->fr_val, qptr,
                      targets, npairs, alpha, lambda, topm,
                      Outputs{sources, positions, contribs, counts, totals, all});
 }

@@ -32,31 +32,17 @@ int qmfx_recommend(qmfx_ctx* c, int64_t nusers, const int64_t* users, int topn, 
   if (set_dev(c)) return -2;
 
   const int64_t ni = c->s[1].n;
-  const size_t lists = (size_t)(eval_chunks(nusers, ni) * eval_user_rows(nusers));
-  const size_t out = (size_t)nusers * (size_t)topn;
-  if (int rc = grow(c->rc_users, c->rc_cap[0], (size_t)nusers * 8)) return rc;
-  if (int rc = grow(c->rc_items, c->rc_cap[1], out * 8)) return rc;
-  if (int rc = grow(c->rc_udbl, c->rc_cap[2], (size_t)(eval_user_rows(nusers) * c->k) * 8)) return rc;
-  if (int rc = grow(c->rc_pscore, c->rc_cap[3], lists * (size_t)topn * 8)) return rc;
-  if (int rc = grow(c->rc_scores, c->rc_cap[4], out * 8)) return rc;
-  if (int rc = grow(c->rc_pitem, c->rc_cap[5], lists * (size_t)topn * 4)) return rc;
-  if (int rc = grow(c->rc_pcnt, c->rc_cap[6], lists * 4)) return rc;
-  if (int rc = grow(c->rc_counts, c->rc_cap[7], (size_t)nusers * 4)) return rc;
-  HIPCHK(scopy(c, c->rc_users, users, (size_t)nusers * 8, hipMemcpyHostToDevice));
+  if (int rc = topn_reserve(c, nusers, ni, topn)) return rc;
+  HIPCHK(scopy(c, c->rc.users, users, (size_t)nusers * 8, hipMemcpyHostToDevice));
 
   HIPCHK(hipEventRecord(c->ev0, c->stream));
   const int rc = with_prec(c->prec, [&](auto t) {
     using T = decltype(t);
     RecArgs<T> a{};
+    topn_args(c, a, nusers, ni, topn);
     a.U = c->s[0].F.as<T>();
     a.I = c->s[1].F.as<T>();
     a.bias = use_biases ? c->bias.as<T>() : nullptr;
-    a.users = c->rc_users;
-    a.nreq = nusers;
-    a.nitems = ni;
-    a.k = c->k;
-    a.kp = c->kp;
-    a.topn = topn;
     if (exclude == QMFX_REC_UNSEEN_SIGNALS) {
       a.seen_ptr = su.rowptr;
       a.seen_col = colp(su);
@@ -64,27 +50,16 @@ int qmfx_recommend(qmfx_ctx* c, int64_t nusers, const int64_t* users, int topn, 
       a.seen_ptr = c->urowptr;
       a.seen_col = c->uitems;
     }
-    a.udbl = c->rc_udbl;
-    a.part_score = c->rc_pscore;
-    a.part_item = c->rc_pitem;
-    a.part_cnt = c->rc_pcnt;
-    a.items = c->rc_items;
-    a.scores = c->rc_scores;
-    a.counts = c->rc_counts;
     HIPCHK(launch_recommend(a, c->stream));
     return 0;
   });
   if (rc) return rc;
   HIPCHK(hipEventRecord(c->ev1, c->stream));
-  HIPCHK(scopy(c, items, c->rc_items, out * 8, hipMemcpyDeviceToHost));
-  HIPCHK(scopy(c, scores, c->rc_scores, out * 8, hipMemcpyDeviceToHost));
-  HIPCHK(scopy(c, counts, c->rc_counts, (size_t)nusers * 4, hipMemcpyDeviceToHost));
-  // the call's kernels, for qmfx_solve_kernel_stats (one unit = one user × item score: 2k
-  // flop; bytes: the item factors once per group of 32 users)
+  if (int r = topn_copy_out(c, nusers, topn, items, scores, counts)) return r;
+  // the call's kernels, for qmfx_solve_kernel_stats
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->solve.add(ms, 2.0 * (double)nusers * (double)ni * c->k,
-               (double)((nusers + 31) / 32) * (double)ni * c->k * (double)c->esz);
+  c->solve.add(ms, topn_flops(c, nusers, ni), topn_bytes(c, nusers, ni));
   return 0;
 }
 

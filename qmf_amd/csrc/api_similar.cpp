@@ -11,7 +11,7 @@ namespace {
 // would have to invalidate a cached copy, and the pass costs about one query)
 int compute_norms(qmfx_ctx* c, int side) {
   const SideBuf& sb = c->s[side];
-  if (int rc = grow(c->sim_norms, c->sim_cap, (size_t)sb.n * 8)) return rc;
+  if (int rc = reserve(c->sim_norms, (size_t)sb.n * 8)) return rc;
   return with_prec(c->prec, [&](auto t) {
     using T = decltype(t);
     HIPCHK(launch_factor_norms(sb.F.as<T>(), sb.n, c->k, c->kp, c->sim_norms, c->stream));
@@ -46,18 +46,8 @@ int qmfx_similar(qmfx_ctx* c, int side, int64_t nq, const int64_t* rows, int top
     if (rows[t] < 0 || rows[t] >= sb.n) return fail("row index out of range");
   if (set_dev(c)) return -2;
 
-  // the selection's scratch is qmfx_recommend's
-  const size_t lists = (size_t)(eval_chunks(nq, sb.n) * eval_user_rows(nq));
-  const size_t out = (size_t)nq * (size_t)topn;
-  if (int rc = grow(c->rc_users, c->rc_cap[0], (size_t)nq * 8)) return rc;
-  if (int rc = grow(c->rc_items, c->rc_cap[1], out * 8)) return rc;
-  if (int rc = grow(c->rc_udbl, c->rc_cap[2], (size_t)(eval_user_rows(nq) * c->k) * 8)) return rc;
-  if (int rc = grow(c->rc_pscore, c->rc_cap[3], lists * (size_t)topn * 8)) return rc;
-  if (int rc = grow(c->rc_scores, c->rc_cap[4], out * 8)) return rc;
-  if (int rc = grow(c->rc_pitem, c->rc_cap[5], lists * (size_t)topn * 4)) return rc;
-  if (int rc = grow(c->rc_pcnt, c->rc_cap[6], lists * 4)) return rc;
-  if (int rc = grow(c->rc_counts, c->rc_cap[7], (size_t)nq * 4)) return rc;
-  HIPCHK(scopy(c, c->rc_users, rows, (size_t)nq * 8, hipMemcpyHostToDevice));
+  if (int rc = topn_reserve(c, nq, sb.n, topn)) return rc;
+  HIPCHK(scopy(c, c->rc.users, rows, (size_t)nq * 8, hipMemcpyHostToDevice));
 
   HIPCHK(hipEventRecord(c->ev0, c->stream));
   if (metric == QMFX_SIM_COSINE)
@@ -65,21 +55,9 @@ int qmfx_similar(qmfx_ctx* c, int side, int64_t nq, const int64_t* rows, int top
   const int rc = with_prec(c->prec, [&](auto t) {
     using T = decltype(t);
     SimArgs<T> a{};
+    topn_args(c, a, nq, sb.n, topn);
     a.U = sb.F.as<T>();
     a.I = sb.F.as<T>();
-    a.users = c->rc_users;
-    a.nreq = nq;
-    a.nitems = sb.n;
-    a.k = c->k;
-    a.kp = c->kp;
-    a.topn = topn;
-    a.udbl = c->rc_udbl;
-    a.part_score = c->rc_pscore;
-    a.part_item = c->rc_pitem;
-    a.part_cnt = c->rc_pcnt;
-    a.items = c->rc_items;
-    a.scores = c->rc_scores;
-    a.counts = c->rc_counts;
     a.norms = c->sim_norms;
     a.cosine = metric == QMFX_SIM_COSINE;
     a.exclude_self = exclude_self != 0;
@@ -88,15 +66,11 @@ int qmfx_similar(qmfx_ctx* c, int side, int64_t nq, const int64_t* rows, int top
   });
   if (rc) return rc;
   HIPCHK(hipEventRecord(c->ev1, c->stream));
-  HIPCHK(scopy(c, neighbours, c->rc_items, out * 8, hipMemcpyDeviceToHost));
-  HIPCHK(scopy(c, scores, c->rc_scores, out * 8, hipMemcpyDeviceToHost));
-  HIPCHK(scopy(c, counts, c->rc_counts, (size_t)nq * 4, hipMemcpyDeviceToHost));
-  // the call's kernels, for qmfx_solve_kernel_stats (one unit = one query × row pair: 2k flop;
-  // bytes: the side's factors once per group of 32 queries)
+  if (int r = topn_copy_out(c, nq, topn, neighbours, scores, counts)) return r;
+  // the call's kernels, for qmfx_solve_kernel_stats
   float ms = 0.f;
   HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-  c->solve.add(ms, 2.0 * (double)nq * (double)sb.n * c->k,
-               (double)((nq + 31) / 32) * (double)sb.n * c->k * (double)c->esz);
+  c->solve.add(ms, topn_flops(c, nq, sb.n), topn_bytes(c, nq, sb.n));
   return 0;
 }
 

@@ -4,7 +4,7 @@
 // RCCL group while piece j+1 computes.
 #include <cstdio>
 
-#include "ctx.h"
+#include "rows.h"
 
 using namespace qmfx;
 
@@ -20,36 +20,6 @@ int ensure_rowloss(qmfx_ctx* c, int64_t n) {
 }
 
 ncclDataType_t nccl_type(int prec) { return prec == 32 ? ncclFloat32 : ncclFloat64; }
-
-// The row kernels' arguments for `n` slots from `b` of L's order, gathering rows of Y.
-template <typename T>
-SolveArgs<T> solve_args(qmfx_ctx* c, const SideBuf& L, const T* Y, int32_t zrow, int64_t b,
-                        int64_t n, uint64_t* trace) {
-  return SolveArgs<T>{L.rowptr, colp(L), valp<T>(L), Y, nullptr, L.F.as<T>(), c->rowloss,
-                      c->status, L.d_order, b, n, (T)c->hs.alpha, (T)c->hs.lambda, c->k,
-                      L.d_desc, nullptr, trace, zrow};
-}
-
-// One launch of the direct-row kernels over `n` slots from `b`: seg_mode 0 = slots of the
-// side's order (rows), 1 = split-K segments (d_seg), 2 = split-K heavy-row solves (d_heavy).
-template <typename T>
-int launch_direct(qmfx_ctx* c, const SideBuf& L, const SideBuf& R, int64_t b, int64_t n,
-                  bool trace, int mode) {
-  if (n <= 0) return 0;
-  SolveArgs<T> a = solve_args<T>(c, L, R.F.as<T>(), (int32_t)R.n, b, n,
-                                 (trace && mode == 0) ? c->trace.get() : nullptr);
-  a.G = c->G.as<T>();
-  a.desc = mode == 1 ? L.d_seg.get() : mode == 2 ? L.d_heavy.get() : L.d_desc.get();
-  a.Gimg = c->Gimg.as<T>();
-  a.seg_mode = mode;
-  a.part = c->part.as<T>();
-  a.partb = c->partb.as<T>();
-  a.partc = c->partc;
-  const hipError_t e = use_big_rows(c) ? launch_wals_big(a, c->nt, c->stream)
-                                       : launch_wals_direct(a, c->nt, c->stream);
-  if (e != hipSuccess) return fail(std::string("row kernel launch: ") + hipGetErrorString(e), -2);
-  return 0;
-}
 
 // G = YᵀY, the whitening and G + λI images, status resets (no collectives)
 template <typename T>
@@ -85,57 +55,20 @@ int half_begin(qmfx_ctx* c, int side, double alpha, double lambda) {
   return with_prec(c->prec, [&](auto t) { return half_begin_t<decltype(t)>(c, side, alpha, lambda); });
 }
 
-// the row solves of piece j (direct, heavy, whitened, pivoted re-solve); records evp[j][2]
+// the row solves of piece j (direct, heavy, whitened, pivoted re-solve before the all-gather);
+// records evp[j][0..2]: start, direct done, whitened done
 template <typename T>
 int half_piece_t(qmfx_ctx* c, int j) {
   if (set_dev(c)) return -2;
-  const int side = c->hs.side;
-  const double alpha = c->hs.alpha, lambda = c->hs.lambda;
-  const bool use_w = c->hs.use_w, trace = c->hs.trace_path != nullptr;
-  SideBuf& L = c->s[side];
-  SideBuf& R = c->s[1 - side];
+  const qmfx_ctx::HalfStateT& hs = c->hs;
+  SideBuf& L = c->s[hs.side];
   const Piece& pc = L.pieces[j];
-  // direct rows (heaviest first; the split-K heavy rows lead); all rows when the whitened
-  // form is off
-  const int64_t dh = pc.ord + pc.wb[kMaxNTN];
-  c->hs.nD += pc.ord + pc.n_ord - (use_w ? dh : pc.ord);
+  c->hs.nD += pc.n_ord - (hs.use_w ? pc.wb[kMaxNTN] : 0);
   HIPCHK(hipEventRecord(c->evp[j][0], c->stream));
-  if (pc.nh > 0) {
-    // heavy rows: segment Grams (one wave per segment), fixed-order fp64 reduction into
-    // each row's first segment, then the row solves from those images
-    if (int rc = launch_direct<T>(c, L, R, pc.s0, pc.ns, false, 1)) return rc;
-    if (use_big_rows(c))
-      // multi-wave tilings: G + λI's image is built here (the direct kernels' Gimg is not)
-      HIPCHK(launch_heavy_reduce_big(c->part.as<T>(), c->partb.as<T>(), c->partc, L.d_hseg, pc.h0,
-                                     pc.nh, c->G.as<const T>(), c->Gimg.as<T>(), c->nt, c->k,
-                                     lambda, c->stream));
-    else
-      HIPCHK(launch_heavy_reduce(c->part.as<T>(), c->partb.as<T>(), c->partc, L.d_hseg, pc.h0,
-                                 pc.nh, c->Gimg.as<const T>(), c->nt, c->stream));
-    if (int rc = launch_direct<T>(c, L, R, pc.h0, pc.nh, false, 2)) return rc;
-  }
-  if (!use_w && pc.wb[kMaxNTN] > 0) {
-    if (int rc = launch_direct<T>(c, L, R, pc.ord, pc.wb[kMaxNTN], trace, 0)) return rc;
-  }
-  if (int rc = launch_direct<T>(c, L, R, dh + pc.nh, pc.ord + pc.n_ord - dh - pc.nh, trace, 0))
+  if (int rc = solve_rows<T>(c, side_rows<T>(c, L), c->s[1 - hs.side], pc.ord, pc.n_ord, pc.wb,
+                             hs.alpha, hs.lambda, hs.use_w, SplitK{&L, pc.nh, pc.h0, pc.s0, pc.ns},
+                             hs.trace_path ? c->trace.get() : nullptr, c->evp[j][1]))
     return rc;
-  HIPCHK(hipEventRecord(c->evp[j][1], c->stream));
-  // whitened rows: per-bucket row solve, then x = L⁻ᵀ x' and −λ‖x‖²
-  if (use_w && pc.wb[kMaxNTN] > 0) {
-    for (int b = 0; b < kMaxNTN; ++b) {
-      const int64_t cnt = pc.wb[b + 1] - pc.wb[b];
-      if (cnt <= 0) continue;
-      const SolveArgs<T> a = solve_args<T>(c, L, c->Z.as<T>(), (int32_t)c->z_cap, pc.ord + pc.wb[b],
-                                           cnt, trace ? c->trace.get() : nullptr);
-      HIPCHK(launch_wals_woodbury(a, c->nt, b + 1, c->stream));
-    }
-    HIPCHK(launch_whiten(L.F.as<const T>(), L.F.as<T>(), L.d_order + pc.ord, pc.wb[kMaxNTN], c->nt,
-                         c->Linv.as<const T>(), c->rowloss, lambda, true, c->cus, c->stream));
-  }
-  // rows the Cholesky kernels flagged: pivoted fp64 re-solve before the all-gather
-  if (pc.n_ord > 0)
-    HIPCHK(launch_wals_fallback(fallback_args<T>(c, L, R, pc.ord, pc.n_ord, alpha, lambda),
-                                c->stream));
   HIPCHK(hipEventRecord(c->evp[j][2], c->stream));
   return 0;
 }
@@ -214,15 +147,9 @@ int half_end(qmfx_ctx* c, double* loss_sum) {
   SideBuf& L = c->s[c->hs.side];
   const int P = (int)L.pieces.size();
   HIPCHK(hipEventRecord(c->evh[2], c->stream));
-  // one small copy into pinned memory
-  HIPCHK(hipMemcpyAsync(c->hsum, c->dsum + kHalfStatus, 4 * sizeof(double),
-                        hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int rc = read_half_status(c)) return rc;
   c->fb_rows = (int64_t)c->hsum[1];
-  // the reference's CHECK(info == 0) after dsysv_ (Matrix.cpp:94)
-  if (c->hsum[2] != 0.0)
-    return fail(std::to_string((int64_t)c->hsum[2]) + " singular row system(s) (dsysv info > 0)", -6);
-  if (c->hsum[3] != 0.0) return fail("YᵀY + λI is not positive definite", -5);
+  if (int rc = half_status_failure(c)) return rc;
   // timing and algorithmic work per kernel class (SURVEY.md §8(d) accounting)
   float ms_d = 0.f, ms_w = 0.f, ms_h = 0.f;
   for (int j = 0; j < P; ++j) {
@@ -260,8 +187,8 @@ int half_end(qmfx_ctx* c, double* loss_sum) {
   const double nzw = use_w ? L.nnz_w : 0.0, nw = use_w ? (double)nW : 0.0;
   double fl_d = 0, by_d = 0, fl_w = 0, by_w = 0;
   if (nD > 0) {
-    fl_d = nzd * k * (k + 1) + nzd * 2 * k + nd * (k * k * k / 3.0 + 2 * k * k);
-    by_d = nzd * (4 + s) + nzd * k * s + nd * k * s + (nd + 1) * 8;
+    fl_d = direct_flops(c, nzd, nd);
+    by_d = direct_bytes(c, nzd, nd);
     acc(0, ms_d, fl_d, by_d);
   }
   if (nW > 0 && use_w) {
@@ -416,8 +343,8 @@ int qmfx_wals_row_system(qmfx_ctx* c, int side, int64_t row, double alpha, doubl
     using T = decltype(t);
     // YᵀY of this side's fixed side (the last half may have solved the other side)
     HIPCHK(launch_gram_t<T>(c, R));
-    hipError_t e = launch_wals_system(fallback_args<T>(c, L, R, 0, 0, alpha, lambda), beg, end, d,
-                                      c->stream);
+    hipError_t e = launch_wals_system(
+        fallback_args<T>(c, side_rows<T>(c, L), R, 0, 0, alpha, lambda), beg, end, d, c->stream);
     if (e == hipSuccess) e = scopy(c, h.data(), d, nout * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(std::string("qmfx_wals_row_system: ") + hipGetErrorString(e), -2);
     return 0;

@@ -110,6 +110,14 @@ struct SideBuf {
   int64_t nseg = 0, nheavy = 0;
 };
 
+// Scratch of the top-N selection (RecArgs; topn_* below): the uploaded request rows, one
+// batch's rows in double, the per-chunk survivor lists and the outputs.
+struct TopN {
+  Scratch<int64_t> users, items;
+  Scratch<double> udbl, pscore, scores;
+  Scratch<int32_t> pitem, pcnt, counts;
+};
+
 }  // namespace qmfx
 
 // Members are destroyed last to first: the streams stand first, so they outlive every buffer
@@ -162,42 +170,34 @@ struct qmfx_ctx {
   qmfx::DevPtr<double> ev_lscore, ev_pscore;
   qmfx::DevPtr<unsigned long long> ev_above;
   qmfx::DevPtr<double> ev_sq, ev_udbl;
-  // top-N recommendations (qmfx_recommend; qmfx_similar shares it): scratch grown on demand (rc_cap: bytes held, in
-  // the members' order)
-  qmfx::DevPtr<int64_t> rc_users, rc_items;
-  qmfx::DevPtr<double> rc_udbl, rc_pscore, rc_scores;
-  qmfx::DevPtr<int32_t> rc_pitem, rc_pcnt, rc_counts;
-  size_t rc_cap[8] = {};
-  // fold-in (qmfx_wals_fold_in, qmfx_recommend_fold_in): the uploaded foreign rows, their plan
-  // and their own output rows, row losses and status words; scratch grown on demand (fi_cap:
-  // bytes held, in the members' order).  fi_classes / fi_n: the last call's plan.
-  qmfx::DevPtr<int64_t> fi_rowptr;
-  qmfx::DevPtr<int32_t> fi_col;
-  qmfx::DevPtr<void> fi_val, fi_X;
-  qmfx::DevPtr<double> fi_rowloss;
-  qmfx::DevPtr<int32_t> fi_status;
-  qmfx::DevPtr<uint64_t> fi_keys, fi_keys2;
-  qmfx::DevPtr<int64_t> fi_order;
-  qmfx::DevPtr<qmfx::RowDesc> fi_desc;
-  qmfx::DevPtr<int64_t> fi_wb;
-  qmfx::DevPtr<double> fi_out;
-  size_t fi_cap[12] = {};
+  // The serving calls' scratch: every buffer knows the bytes it holds and is grown on demand
+  // (reserve).  Top-N selection (qmfx_recommend, qmfx_similar, qmfx_recommend_fold_in):
+  qmfx::TopN rc;
+  // rows given with a call as a CSR of their own (fold-in, qmfx_wals_explain_rows): the last
+  // upload (upload_rows, rows.h)
+  qmfx::Scratch<int64_t> fr_rowptr;
+  qmfx::Scratch<int32_t> fr_col;
+  qmfx::Scratch<void> fr_val;
+  // fold-in (qmfx_wals_fold_in, qmfx_recommend_fold_in): the uploaded rows' plan and their own
+  // output rows, row losses and status words.  fi_classes / fi_n: the last fold-in's plan.
+  qmfx::Scratch<void> fi_X;
+  qmfx::Scratch<double> fi_rowloss;
+  qmfx::Scratch<int32_t> fi_status;
+  qmfx::Scratch<uint64_t> fi_keys, fi_keys2;
+  qmfx::Scratch<int64_t> fi_order;
+  qmfx::Scratch<qmfx::RowDesc> fi_desc;
+  qmfx::Scratch<int64_t> fi_wb;
+  qmfx::Scratch<double> fi_out;
   int64_t fi_classes[qmfx::kMaxNTN + 3] = {};
   int64_t fi_n = -1;  // rows of the last plan (-1: no fold-in yet)
-  // explanations (qmfx_wals_explain, qmfx_wals_explain_rows): the uploaded queries (and, for
-  // the rows form, the rows' CSR), the outputs and the KP > 128 factor scratch; grown on demand
-  // (ex_cap: bytes held, in the members' order)
-  qmfx::DevPtr<int64_t> ex_rows, ex_qptr, ex_targets, ex_allq, ex_rowptr;
-  qmfx::DevPtr<int32_t> ex_col;
-  qmfx::DevPtr<void> ex_val;
-  qmfx::DevPtr<int64_t> ex_sources, ex_positions;
-  qmfx::DevPtr<double> ex_contribs, ex_totals, ex_all, ex_scratch;
-  qmfx::DevPtr<int32_t> ex_counts;
-  qmfx::DevPtr<unsigned long long> ex_first;
-  size_t ex_cap[15] = {};
+  // explanations (qmfx_wals_explain, qmfx_wals_explain_rows): the uploaded queries, the
+  // outputs and the KP > 128 factor scratch
+  qmfx::Scratch<int64_t> ex_rows, ex_qptr, ex_targets, ex_allq, ex_sources, ex_positions;
+  qmfx::Scratch<double> ex_contribs, ex_totals, ex_all, ex_scratch;
+  qmfx::Scratch<int32_t> ex_counts;
+  qmfx::Scratch<unsigned long long> ex_first;
   // similar rows (qmfx_similar, qmfx_factor_norms): one side's row norms, written by every call
-  qmfx::DevPtr<double> sim_norms;
-  size_t sim_cap = 0;
+  qmfx::Scratch<double> sim_norms;
   uint64_t bpr_epochs = 0;
   // QMFX_FAULT_COMM_RANK=<rank>[:<after>] (tests), read once at create: that rank's piece
   // broadcasts fail as if RCCL had failed once <after> of them have succeeded (-1: none)
@@ -302,12 +302,63 @@ inline hipError_t copy_out(qmfx_ctx* c, double* dst, const void* src, size_t n) 
 
 // scratch grown on demand: keeps the buffer when it already holds `bytes`
 template <typename T>
-int grow(DevPtr<T>& p, size_t& cap, size_t bytes) {
-  if (p && cap >= bytes) return 0;
-  cap = 0;
+int reserve(Scratch<T>& p, size_t bytes) {
+  if (p && p.bytes >= bytes) return 0;
+  p.bytes = 0;
   HIPCHK(dev_alloc(p, bytes));
-  cap = bytes;
+  p.bytes = bytes;
   return 0;
+}
+
+// The top-N selection's scratch for nreq request rows over ncand candidate rows.
+inline int topn_reserve(qmfx_ctx* c, int64_t nreq, int64_t ncand, int topn) {
+  TopN& s = c->rc;
+  const size_t n = (size_t)nreq, out = n * (size_t)topn;
+  const size_t lists = (size_t)(eval_chunks(nreq, ncand) * eval_user_rows(nreq));
+  if (int rc = reserve(s.users, n * 8)) return rc;
+  if (int rc = reserve(s.items, out * 8)) return rc;
+  if (int rc = reserve(s.udbl, (size_t)(eval_user_rows(nreq) * c->k) * 8)) return rc;
+  if (int rc = reserve(s.pscore, lists * (size_t)topn * 8)) return rc;
+  if (int rc = reserve(s.scores, out * 8)) return rc;
+  if (int rc = reserve(s.pitem, lists * (size_t)topn * 4)) return rc;
+  if (int rc = reserve(s.pcnt, lists * 4)) return rc;
+  return reserve(s.counts, n * 4);
+}
+// What every selection sets the same way (SimArgs derives from RecArgs); the caller adds
+// U, I and what is its own.
+template <typename T>
+void topn_args(qmfx_ctx* c, RecArgs<T>& a, int64_t nreq, int64_t ncand, int topn) {
+  const TopN& s = c->rc;
+  a.users = s.users;
+  a.nreq = nreq;
+  a.nitems = ncand;
+  a.k = c->k;
+  a.kp = c->kp;
+  a.topn = topn;
+  a.udbl = s.udbl;
+  a.part_score = s.pscore;
+  a.part_item = s.pitem;
+  a.part_cnt = s.pcnt;
+  a.items = s.items;
+  a.scores = s.scores;
+  a.counts = s.counts;
+}
+inline int topn_copy_out(qmfx_ctx* c, int64_t nreq, int topn, int64_t* items, double* scores,
+                         int32_t* counts) {
+  const TopN& s = c->rc;
+  const size_t out = (size_t)nreq * (size_t)topn;
+  HIPCHK(scopy(c, items, s.items, out * 8, hipMemcpyDeviceToHost));
+  HIPCHK(scopy(c, scores, s.scores, out * 8, hipMemcpyDeviceToHost));
+  HIPCHK(scopy(c, counts, s.counts, (size_t)nreq * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+// A selection's work for qmfx_solve_kernel_stats: one unit = one request × candidate score,
+// 2k flop; bytes: the candidates' factors once per group of 32 requests.
+inline double topn_flops(const qmfx_ctx* c, int64_t nreq, int64_t ncand) {
+  return 2.0 * (double)nreq * (double)ncand * c->k;
+}
+inline double topn_bytes(const qmfx_ctx* c, int64_t nreq, int64_t ncand) {
+  return (double)((nreq + 31) / 32) * (double)ncand * c->k * (double)c->esz;
 }
 
 // col/val as the kernels index them: with the global rowptr (see SideBuf::shard_off)
@@ -395,56 +446,6 @@ hipError_t launch_gram_t(qmfx_ctx* c, const SideBuf& R) {
                                   c->gpart_blocks, c->stream);
 }
 
-// The fixed side's part of a half, from its current factors: G = YᵀY, and for the whitened
-// rows (use_w) L⁻¹ of G + λI and Z = Y·L⁻ᵀ; G + λI's tile image for the one-wave direct rows.
-template <typename T>
-int fixed_side_prologue(qmfx_ctx* c, const SideBuf& R, double lambda, bool use_w) {
-  // G = YᵀY of the fixed side (full replica on every rank)
-  HIPCHK(launch_gram_t<T>(c, R));
-  if (use_w) {
-    if (c->z_cap < R.n) {
-      // one extra all-zero row (index z_cap): the whitened kernel's padding signals
-      const int64_t cap = std::max(c->s[0].n, c->s[1].n);
-      HIPCHK(dev_alloc(c->Z, (size_t)(cap + 1) * c->kp * c->esz));
-      HIPCHK(hipMemsetAsync(c->Z.as<char>() + (size_t)cap * c->kp * c->esz, 0,
-                            (size_t)c->kp * c->esz, c->stream));
-      c->z_cap = cap;
-    }
-    HIPCHK(hipMemsetAsync(c->chol_status, 0, 4, c->stream));
-    HIPCHK(launch_chol_inv(c->G.as<const T>(), c->nt, c->k, lambda, c->Linv.as<T>(),
-                           c->chol_status, c->chol_scratch, c->stream));
-    HIPCHK(launch_whiten(R.F.as<const T>(), c->Z.as<T>(), nullptr, R.n, c->nt,
-                         c->Linv.as<const T>(), nullptr, 0.0, false, c->cus, c->stream));
-  }
-  if (!use_big_rows(c))
-    HIPCHK(launch_gimg(c->G.as<const T>(), c->nt, c->k, lambda, c->Gimg.as<T>(), c->stream));
-  return 0;
-}
-
-template <typename T>
-FallbackArgs<T> fallback_args(qmfx_ctx* c, const SideBuf& L, const SideBuf& R, int64_t slot_begin,
-                              int64_t nslots, double alpha, double lambda) {
-  FallbackArgs<T> a{};
-  a.rowptr = L.rowptr;
-  a.col = colp(L);
-  a.val = valp<T>(L);
-  a.Y = R.F.as<T>();
-  a.G = c->G.as<T>();
-  a.X = L.F.as<T>();
-  a.rowloss = c->rowloss;
-  a.status = c->status;
-  a.desc = L.d_desc;
-  a.slot_begin = slot_begin;
-  a.nslots = nslots;
-  a.alpha = alpha;
-  a.lambda = lambda;
-  a.k = c->k;
-  a.kp = c->kp;
-  a.scratch = c->fb_scratch;
-  a.counters = c->fb_cnt;
-  return a;
-}
-
 // api_signals.cpp
 void drop_csr(SideBuf& sb);  // releases the CSR arrays of a side
 void set_default_bounds(SideBuf& sb, int world, int rank);
@@ -452,11 +453,6 @@ void plan_pieces(const std::vector<int64_t>& rp, const std::vector<int64_t>& bou
                  int P, std::vector<int64_t>& pb);
 int build_buckets(qmfx_ctx* c, int side);
 int shard_csr(qmfx_ctx* c, SideBuf& sb);
-
-// api_foldin.cpp: the one host pass over rows given as a CSR of their own: the CSR's shape and
-// every column index (an index out of range would be a device fault).  *max_n: the longest row.
-int validate_rows(int64_t nrows, const int64_t* rowptr, const int32_t* colidx, const double* values,
-                  int64_t nother, bool need_ascending, int64_t* max_n);
 
 // api_eval.cpp
 void drop_eval_labels(qmfx_ctx* c);  // releases the test-label set (qmfx_eval_ranks then fails)

@@ -48,6 +48,12 @@ hipError_t dev_alloc(DevPtr<T>& p, size_t bytes) {
   if (e == hipSuccess) p.reset(static_cast<T*>(raw));
   return e;
 }
+// Device scratch that knows its size: the buffer and the bytes it holds (ctx.h's reserve()
+// grows it on demand).  Converts like the owner it is, so argument code reads the same.
+template <typename T>
+struct Scratch : DevPtr<T> {
+  size_t bytes = 0;
+};
 template <typename T>
 hipError_t pinned_alloc(PinnedPtr<T>& p, size_t bytes) {
   p.reset();
