@@ -191,6 +191,37 @@ int qmfx_recommend(qmfx_ctx* ctx, int64_t nusers, const int64_t* users, int topn
                    int use_biases, int64_t* items /*nusers·topn*/, double* scores /*nusers·topn*/,
                    int32_t* counts /*nusers*/);
 
+/* ---- recommendations within candidate sets -----------------------------------------------------
+ * qmfx_recommend with fewer eligible items.  Scores (bit for bit), order and tie rule, counts[t] =
+ * min(topn, eligible), the -1 / 0.0 tail, the three exclude modes (the own-rows rule of
+ * QMFX_REC_UNSEEN_SIGNALS on a sharded context included) and use_biases are qmfx_recommend's.
+ * qmfx_recommend_without: the ndeny items of `deny` (item idx; any order, repeats allowed) are
+ * eligible for nobody, on top of `exclude`.  The whole catalogue is still scanned: one bit per
+ * item is uploaded and the selection skips the set ones.  ndeny == 0 is qmfx_recommend.
+ * qmfx_recommend_candidates: only listed items are eligible, and only they are scored (their
+ * rows are gathered by index: the work follows the lists' lengths, not the catalogue's).
+ * cptr == NULL: one list cand[0 .. ncand) shared by all requested users; cptr != NULL: user t's
+ * list is cand[cptr[t] .. cptr[t+1]) and ncand is ignored (a repeated user may carry different
+ * lists).  Every list is strictly ascending item idx; an empty list gives count 0.  A shared
+ * list of every item is qmfx_recommend exactly.  A deny list and candidate lists do not combine
+ * in one call: the caller removes denied items from its lists.
+ * Fail (-1, with a message, before anything is launched) on everything qmfx_recommend rejects
+ * and on: ndeny < 0 or ncand < 0, a deny or candidate index out of range, cptr[0] != 0 or cptr
+ * decreasing, a list that is not strictly ascending, 2^31 candidates or more in total.
+ * nusers == 0 succeeds and touches nothing.  The calls leave the factors, CSR, biases and every
+ * cached state untouched; their scratch is sized from the request and owned by the context.
+ * Their kernel time is counted in qmfx_solve_kernel_stats with 2k flop per (user, item scanned)
+ * pair for the deny call and 2k flop per (user, candidate) pair for the candidate call. */
+int qmfx_recommend_without(qmfx_ctx* ctx, int64_t nusers, const int64_t* users, int64_t ndeny,
+                           const int64_t* deny, int topn, int exclude, int use_biases,
+                           int64_t* items /*nusers·topn*/, double* scores /*nusers·topn*/,
+                           int32_t* counts /*nusers*/);
+int qmfx_recommend_candidates(qmfx_ctx* ctx, int64_t nusers, const int64_t* users,
+                              const int64_t* cptr /*NULL or nusers+1*/, int64_t ncand,
+                              const int64_t* cand, int topn, int exclude, int use_biases,
+                              int64_t* items /*nusers·topn*/, double* scores /*nusers·topn*/,
+                              int32_t* counts /*nusers*/);
+
 /* ---- similar rows: top-N neighbours in factor space ----------------------------------------
  * For each of the nq query rows of `side` (row idx; any order, repeats allowed) the device
  * scores every row of the same side against the query row and selects the best eligible ones,

@@ -57,6 +57,10 @@ SIGNATURES = {
     "qmfx_eval_set_labels": [vp, c_i64, P_i64, P_i64, P_i64, P_f64],
     "qmfx_eval_ranks": [vp, c_int, P_f64, P_i64, P_f64],
     "qmfx_recommend": [vp, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64, P_i32],
+    "qmfx_recommend_without": [vp, c_i64, P_i64, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64,
+                               P_i32],
+    "qmfx_recommend_candidates": [vp, c_i64, P_i64, P_i64, c_i64, P_i64, c_int, c_int, c_int,
+                                  P_i64, P_f64, P_i32],
     "qmfx_factor_norms": [vp, c_int, P_f64],
     "qmfx_similar": [vp, c_int, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64, P_i32],
     "qmfx_wals_fold_in": [vp, c_int, c_i64, P_i64, P_i32, P_f64, c_dbl, c_dbl, P_f64, P_f64, P_i64],
@@ -401,6 +405,41 @@ class Context:
         _check(lib().qmfx_recommend(self.h, n, _p(users, P_i64), int(topn), int(exclude),
                                     int(use_biases), _p(items, P_i64), _p(scores, P_f64),
                                     _p(counts, P_i32)))
+        return items, scores, counts
+
+    def _topn_out(self, n, topn):
+        w = max(int(topn), 0)
+        return np.empty((n, w), np.int64), np.empty((n, w), np.float64), np.empty(n, np.int32)
+
+    def recommend_without(self, users, deny, topn, exclude=0, use_biases=False):
+        """recommend() with the item indices `deny` (any order, repeats allowed) eligible for
+        nobody: see include/qmfx.h qmfx_recommend_without."""
+        users = np.ascontiguousarray(users, np.int64)
+        deny = np.ascontiguousarray(deny, np.int64)
+        items, scores, counts = self._topn_out(len(users), topn)
+        _check(lib().qmfx_recommend_without(self.h, len(users), _p(users, P_i64), len(deny),
+                                            _p(deny, P_i64), int(topn), int(exclude),
+                                            int(use_biases), _p(items, P_i64), _p(scores, P_f64),
+                                            _p(counts, P_i32)))
+        return items, scores, counts
+
+    def recommend_candidates(self, users, topn, cand, cptr=None, exclude=0, use_biases=False):
+        """recommend() within candidate lists: `cand` is one strictly ascending list of item
+        indices shared by all users, or with cptr (len(users) + 1 offsets) user t's list is
+        cand[cptr[t]:cptr[t + 1]]: see include/qmfx.h qmfx_recommend_candidates.  The lists are
+        passed through as given, neither sorted nor deduplicated."""
+        users = np.ascontiguousarray(users, np.int64)
+        cand = np.ascontiguousarray(cand, np.int64)
+        ncand = len(cand)
+        if cptr is not None:
+            cptr = np.ascontiguousarray(cptr, np.int64)
+            if len(cptr) != len(users) + 1 or (len(cptr) and cptr.max() > ncand):
+                raise QmfxError("candidate list shape mismatch")
+        items, scores, counts = self._topn_out(len(users), topn)
+        _check(lib().qmfx_recommend_candidates(
+            self.h, len(users), _p(users, P_i64), None if cptr is None else _p(cptr, P_i64),
+            ncand, _p(cand, P_i64), int(topn), int(exclude), int(use_biases), _p(items, P_i64),
+            _p(scores, P_f64), _p(counts, P_i32)))
         return items, scores, counts
 
     # ---- similar rows

@@ -111,11 +111,15 @@ struct SideBuf {
 };
 
 // Scratch of the top-N selection (RecArgs; topn_* below): the uploaded request rows, one
-// batch's rows in double, the per-chunk survivor lists and the outputs.
+// batch's rows in double, the per-chunk survivor lists and the outputs; the deny bitmap of
+// qmfx_recommend_without; the lists and work items of qmfx_recommend_candidates (CandArgs).
 struct TopN {
   Scratch<int64_t> users, items;
   Scratch<double> udbl, pscore, scores;
   Scratch<int32_t> pitem, pcnt, counts;
+  Scratch<unsigned long long> deny;
+  Scratch<int32_t> cand, wuser;
+  Scratch<int64_t> cptr, woff;
 };
 
 }  // namespace qmfx
@@ -310,11 +314,10 @@ int reserve(Scratch<T>& p, size_t bytes) {
   return 0;
 }
 
-// The top-N selection's scratch for nreq request rows over ncand candidate rows.
-inline int topn_reserve(qmfx_ctx* c, int64_t nreq, int64_t ncand, int topn) {
+// The top-N selection's scratch for nreq request rows and `lists` per-chunk survivor lists.
+inline int topn_reserve_lists(qmfx_ctx* c, int64_t nreq, size_t lists, int topn) {
   TopN& s = c->rc;
   const size_t n = (size_t)nreq, out = n * (size_t)topn;
-  const size_t lists = (size_t)(eval_chunks(nreq, ncand) * eval_user_rows(nreq));
   if (int rc = reserve(s.users, n * 8)) return rc;
   if (int rc = reserve(s.items, out * 8)) return rc;
   if (int rc = reserve(s.udbl, (size_t)(eval_user_rows(nreq) * c->k) * 8)) return rc;
@@ -323,6 +326,11 @@ inline int topn_reserve(qmfx_ctx* c, int64_t nreq, int64_t ncand, int topn) {
   if (int rc = reserve(s.pitem, lists * (size_t)topn * 4)) return rc;
   if (int rc = reserve(s.pcnt, lists * 4)) return rc;
   return reserve(s.counts, n * 4);
+}
+// ... over all ncand candidate rows (the dense scan's chunks)
+inline int topn_reserve(qmfx_ctx* c, int64_t nreq, int64_t ncand, int topn) {
+  return topn_reserve_lists(c, nreq, (size_t)(eval_chunks(nreq, ncand) * eval_user_rows(nreq)),
+                            topn);
 }
 // What every selection sets the same way (SimArgs derives from RecArgs); the caller adds
 // U, I and what is its own.

@@ -302,9 +302,33 @@ struct RecArgs {
   int32_t* counts;           // [nreq] out: min(topn, eligible items)
   int64_t chunk;             // set by the launcher
   int64_t t_base, nbatch;    // set by the launcher: first user and user rows of the batch
+  // deny list (qmfx_recommend_without): bit i % 64 of word i / 64 set = item i is eligible for
+  // nobody; nullptr: none.  Only launch_recommend reads it.
+  const unsigned long long* deny;  // [(nitems + 63) / 64]
 };
 hipError_t launch_recommend(const RecArgs<float>& a, hipStream_t s);
 hipError_t launch_recommend(const RecArgs<double>& a, hipStream_t s);
+
+// Top-N within candidate lists (recommend.hip, qmfx_recommend_candidates): the selection of
+// RecArgs over listed items only.  cptr == nullptr: every user ranks the shared list
+// cand[0 .. ncand); else user t ranks cand[cptr[t] .. cptr[t + 1]).  A list is strictly
+// ascending.  A list of n candidates is cut into cand_chunks(n) chunks; the per-user form runs
+// one wave per work item (user, chunk): user t owns the work items woff[t] .. woff[t + 1], and
+// wuser maps a work item back to its user.  Partial lists: shared form
+// [cand_chunks(ncand)][eval_user_rows(nreq)], per-user form one per work item (woff[nreq]).
+int64_t cand_chunks(int64_t n);
+template <typename T>
+struct CandArgs : RecArgs<T> {
+  const int32_t* cand;       // the lists' item rows
+  int64_t ncand;             // shared form: the list's length
+  const int64_t* cptr;       // [nreq + 1] or nullptr
+  const int64_t* woff;       // [nreq + 1] per-user form: first work item of every user
+  const int32_t* wuser;      // [woff[nreq]] per-user form: the user (position in users) of an item
+  const int64_t* h_woff;     // woff on the host (the launcher batches by it)
+  int64_t w_base, w_end;     // set by the launcher: the batch's work items
+};
+hipError_t launch_recommend_candidates(const CandArgs<float>& a, hipStream_t s);
+hipError_t launch_recommend_candidates(const CandArgs<double>& a, hipStream_t s);
 
 // Top-N neighbours of a side's rows among the rows of the same side (recommend.hip): the
 // selection of RecArgs with U = I = the side's factors, users = the query rows, nitems = the

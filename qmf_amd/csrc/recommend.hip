@@ -34,6 +34,11 @@
 // row norms of rec_norms_kernel (sqrt of the same unfused sum), and can leave the query's own
 // row out by index.  Norms are recomputed per call: O(n·k), about one query's work.
 //
+// Narrower catalogues: a deny list (qmfx_recommend_without) is one bit per item that
+// rec_select_kernel's recommend mode ORs into every user's seen mask, a tile's 64 bits being one
+// wave-uniform word; candidate lists (qmfx_recommend_candidates) are cand_select_kernel below,
+// which gathers only the listed rows and shares the append / prune / merge steps.
+//
 // LDS of rec_select_kernel (dynamic, one configuration): 32 lists × 256 × 12 B = 96 KiB, the
 // per-user state 1,280 B, the item tile 64 × 66 × sizeof(T): 133,376 B (fp64) / 116,480 B
 // (fp32), one workgroup per CU.
@@ -53,6 +58,8 @@ constexpr int RC_KC = 64;               // factor columns per LDS stage
 constexpr int RC_KMAX = 256;
 constexpr int RC_TS = RC_KC + 2;        // tile row stride (even: 8-byte aligned pairs)
 constexpr int RC_CAP = 256;             // candidates per list (≥ kRecMaxN + RC_TI)
+constexpr int RC_CHUNK = 512;           // listed candidates per chunk (cand_select_kernel)
+static_assert(RC_CHUNK % RC_TI == 0);
 static_assert(RC_CAP >= kRecMaxN + RC_TI, "a pruned list must take another full tile");
 
 // dynamic LDS carve (every offset a multiple of 16)
@@ -85,12 +92,15 @@ __device__ __forceinline__ double cosine_rn(double dot, double na, double nb) {
 #pragma clang fp contract(on)
 
 // what rec_select_kernel ranks: a user's items by score (qmfx_recommend), or a row's
-// neighbours on its own side by dot product or cosine (qmfx_similar)
+// neighbours on its own side by dot product or cosine (qmfx_similar); SEL_RECOMMEND_DENY is
+// SEL_RECOMMEND with a deny bitmap (a mode of its own, so that the kernel without one stays
+// exactly the code it was)
 // (plain ints: an unnamed enum in the kernel's signature is mangled differently by the host
 // and the device compilation, and the launch then finds no kernel)
-constexpr int SEL_RECOMMEND = 0, SEL_SIM_DOT = 1, SEL_SIM_COSINE = 2;
+constexpr int SEL_RECOMMEND = 0, SEL_SIM_DOT = 1, SEL_SIM_COSINE = 2, SEL_RECOMMEND_DENY = 3;
+constexpr bool sel_is_sim(int mode) { return mode == SEL_SIM_DOT || mode == SEL_SIM_COSINE; }
 template <typename T, int Mode>
-using SelArgs = std::conditional_t<Mode == SEL_RECOMMEND, RecArgs<T>, SimArgs<T>>;
+using SelArgs = std::conditional_t<sel_is_sim(Mode), SimArgs<T>, RecArgs<T>>;
 
 // (score a, item a) ranks before (score b, item b)
 __device__ __forceinline__ bool rec_before(double sa, int32_t ia, double sb, int32_t ib) {
@@ -196,7 +206,8 @@ __global__ __launch_bounds__(256) void rec_norms_kernel(const T* __restrict__ F,
   norms[r] = __builtin_sqrt(s);  // correctly rounded (no fast-math in this build)
 }
 
-// Mode SEL_RECOMMEND is qmfx_recommend's kernel.  The similarity modes (a.U == a.I, no bias, no
+// Mode SEL_RECOMMEND is qmfx_recommend's kernel, SEL_RECOMMEND_DENY the same with the tile's
+// word of the deny bitmap ORed into every user's seen mask.  The similarity modes (a.U == a.I, no bias, no
 // seen lists) differ after the dot accumulation only: cosine divides by the two rows' norms,
 // and with exclude_self the lane whose row is the query's own row does not propose.
 template <typename T, int Mode>
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(256) void rec_select_kernel(SelArgs<T, Mode> a) {
   // wave-uniform rows, read through the constant address space so they become scalar loads
   typedef const __attribute__((address_space(4))) double* cdptr;
   const cdptr ud = (cdptr)(a.udbl + (tw - a.t_base) * a.k);  // [f][8] for this wave's users
-  constexpr bool kSim = Mode != SEL_RECOMMEND;
+  constexpr bool kSim = sel_is_sim(Mode);
 
   // The state of this wave's users (only this wave touches it, so no barrier orders it):
   // an empty list without threshold, and the seen-list cursor at the chunk's first item.
@@ -314,8 +325,15 @@ __global__ __launch_bounds__(256) void rec_select_kernel(SelArgs<T, Mode> a) {
       }
     }
 
-    // proposals: valid, unseen (similarity: not the query's own row) and ranking before the
-    // user's threshold
+    // the tile's word of the deny bitmap (tiles start on multiples of 64 items): wave-uniform
+    unsigned long long denied = 0ull;
+    if constexpr (Mode == SEL_RECOMMEND_DENY) {
+      typedef const __attribute__((address_space(4))) unsigned long long* cwptr;
+      denied = ((cwptr)a.deny)[ib >> 6];
+    }
+
+    // proposals: valid, unseen and not denied (similarity: not the query's own row) and ranking
+    // before the user's threshold
     double cn = 0.0;  // this lane's row norm
     if constexpr (Mode == SEL_SIM_COSINE) cn = valid ? a.norms[item] : 0.0;
 #pragma unroll
@@ -334,7 +352,7 @@ __global__ __launch_bounds__(256) void rec_select_kernel(SelArgs<T, Mode> a) {
           acc[g] = cosine_rn(acc[g], ((cdptr)a.norms)[q], cn);
         if (a.exclude_self) self = q;
       }
-      const bool seen = kSim ? item == self : (bool)((st_seen[u] >> lane) & 1ull);
+      const bool seen = kSim ? item == self : (bool)(((st_seen[u] | denied) >> lane) & 1ull);
       const bool propose = valid && !seen && (thi < 0 || rec_before(acc[g], item32, ths, thi));
       const RecList L{cand_s + u * RC_CAP, cand_i + u * RC_CAP};
       const int n = rec_append(L, cnt, propose, acc[g], item32);
@@ -385,6 +403,9 @@ struct RecMergeArgs {
   int64_t* items;
   double* scores;
   int32_t* counts;
+  // nullptr: user tr's lists are the slots ch · nbatch + tr, ch < nchunk; else the slots
+  // woff[t] .. woff[t + 1] (cand_select_kernel's per-user form)
+  const int64_t* woff;
 };
 
 __global__ __launch_bounds__(64) void rec_merge_kernel(RecMergeArgs a) {
@@ -398,8 +419,14 @@ __global__ __launch_bounds__(64) void rec_merge_kernel(RecMergeArgs a) {
   int cnt = 0;
   int32_t thi = -1;
   double ths = 0.0;
+  int64_t nchunk = a.nchunk, slot0 = tr, stride = a.nbatch;
+  if (a.woff) {
+    slot0 = a.woff[t];
+    nchunk = a.woff[t + 1] - slot0;
+    stride = 1;
+  }
   // the chunks' slots [chunk][topn] as one list, 64 slots at a time
-  const int64_t total = a.nchunk * a.topn;
+  const int64_t total = nchunk * a.topn;
   for (int64_t e0 = 0; e0 < total; e0 += 64) {
     const int64_t e = e0 + lane;
     bool valid = e < total;
@@ -408,7 +435,7 @@ __global__ __launch_bounds__(64) void rec_merge_kernel(RecMergeArgs a) {
     if (valid) {
       const int64_t ch = e / a.topn;
       const int64_t j = e - ch * a.topn;
-      const int64_t slot = ch * a.nbatch + tr;
+      const int64_t slot = slot0 + ch * stride;
       valid = j < a.part_cnt[slot];
       if (valid) {
         s = a.part_score[slot * a.topn + j];
@@ -459,7 +486,243 @@ hipError_t select(const SelArgs<T, Mode>& a0, hipStream_t s) {
     hipLaunchKernelGGL((rec_select_kernel<T, Mode>), dim3((unsigned)nchunk, (unsigned)ng),
                        dim3(256), rec_lds_bytes<T>(), s, a);
     const RecMergeArgs m{a.part_score, a.part_item, a.part_cnt, nchunk, a.nbatch, a.t_base,
-                         a.nreq,       a.topn,      a.items,    a.scores, a.counts};
+                         a.nreq,       a.topn,      a.items,    a.scores, a.counts,
+                         nullptr};
+    hipLaunchKernelGGL(rec_merge_kernel, dim3((unsigned)nu), dim3(64), 0, s, m);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// ---- candidate lists (qmfx_recommend_candidates) ---------------------------------------------
+// The selection of rec_select_kernel over listed items only: rows of I are gathered by index,
+// so the work follows the lists' lengths, never the catalogue's.  Lists are cut into chunks of
+// RC_CHUNK candidates whose ≤ N survivors go through the partial lists and rec_merge_kernel.
+//   Shared list   grid (chunks, groups of 32 users): the dense kernel's shape, 4 waves of 8
+//                 users over one tile of 64 gathered rows staged through LDS in 64-column
+//                 stages (one wave's load instruction reads 64 columns of one row: 256 / 512
+//                 contiguous bytes).
+//   Per-user      one wave per work item (user, chunk), 4 independent waves per workgroup and
+//                 no barrier: every lane reads its own candidate's row from global memory, 8
+//                 values at a time, with the user's row wave-uniform through the scalar cache.
+//                 No tile, so 12 KiB of LDS and several workgroups per CU hide the gather.
+// Seen items: a lane whose candidate would be proposed binary-searches the user's ascending
+// seen list for it (few lanes once the threshold stands).
+template <bool Shared>
+struct CandShape {
+  static constexpr int UW = Shared ? RC_UW : 1;  // users per wave
+  static constexpr int NU = UW * RC_W;           // lists per workgroup
+  // dynamic LDS carve (every offset a multiple of 16)
+  static constexpr int OFF_CI = NU * RC_CAP * 8;            // int32 [NU][256] items
+  static constexpr int OFF_THR = OFF_CI + NU * RC_CAP * 4;  // double [NU] threshold scores
+  static constexpr int OFF_THI = OFF_THR + NU * 8;          // int32 [NU] threshold item (−1: none)
+  static constexpr int OFF_CNT = OFF_THI + NU * 4;          // int32 [NU] candidates held
+  static constexpr int OFF_TILE = OFF_CNT + NU * 4;         // shared form: the gathered tile
+  static_assert(OFF_TILE % 16 == 0);
+  template <typename T>
+  static constexpr int lds_bytes() {
+    return OFF_TILE + (Shared ? RC_TI * RC_TS * (int)sizeof(T) : 0);
+  }
+};
+static_assert(CandShape<true>::lds_bytes<double>() <= 160 * 1024);
+
+// is `item` in the ascending list col[lo .. end)?
+__device__ __forceinline__ bool cand_seen(const int32_t* __restrict__ col, int64_t lo, int64_t end,
+                                          int32_t item) {
+  int64_t hi = end;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (col[mid] < item)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo < end && col[lo] == item;
+}
+
+template <typename T, bool Shared>
+__global__ __launch_bounds__(256) void cand_select_kernel(CandArgs<T> a) {
+  using S = CandShape<Shared>;
+  constexpr int UW = S::UW;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* const cand_s = (double*)smem;
+  int32_t* const cand_i = (int32_t*)(smem + S::OFF_CI);
+  double* const st_thr = (double*)(smem + S::OFF_THR);
+  int32_t* const st_thi = (int32_t*)(smem + S::OFF_THI);
+  int32_t* const st_cnt = (int32_t*)(smem + S::OFF_CNT);
+  [[maybe_unused]] T* const tile = (T*)(smem + S::OFF_TILE);
+
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // this wave's users tw .. tw + UW (positions in the request), its candidates cand[c0 .. c1)
+  // and the partial list of its first user
+  int64_t tw, c0, c1, slot0;
+  if constexpr (Shared) {
+    tw = a.t_base + (int64_t)blockIdx.y * RC_UG + w * RC_UW;
+    c0 = (int64_t)blockIdx.x * RC_CHUNK;
+    c1 = c0 + RC_CHUNK < a.ncand ? c0 + RC_CHUNK : a.ncand;
+    slot0 = (int64_t)blockIdx.x * a.nbatch + (tw - a.t_base);
+  } else {
+    const int64_t wi = a.w_base + (int64_t)blockIdx.x * RC_W + w;
+    if (wi >= a.w_end) return;  // a whole wave; this form has no barrier
+    tw = uniform((int64_t)a.wuser[wi]);
+    const int64_t b = uniform(a.cptr[tw]), e = uniform(a.cptr[tw + 1]);
+    c0 = b + (wi - uniform(a.woff[tw])) * RC_CHUNK;
+    c1 = c0 + RC_CHUNK < e ? c0 + RC_CHUNK : e;
+    slot0 = wi;
+  }
+  typedef const __attribute__((address_space(4))) double* cdptr;
+  // user tw + g at factor f: ud[f · 8 + g] (rec_users_kernel's layout)
+  const int64_t tr = tw - a.t_base;
+  const cdptr ud = (cdptr)(a.udbl + (tr / RC_UW) * a.k * RC_UW + (tr % RC_UW));
+
+  if (lane < UW) {
+    const int u = w * UW + lane;
+    st_cnt[u] = 0;
+    st_thi[u] = -1;
+    st_thr[u] = 0.0;
+  }
+
+  for (int64_t p0 = c0; p0 < c1; p0 += RC_TI) {
+    const bool valid = p0 + lane < c1;
+    const int32_t item = valid ? a.cand[p0 + lane] : 0;  // row 0 exists: some list is not empty
+    double acc[UW];
+    const double b0 = (a.bias && valid) ? (double)a.bias[item] : 0.0;
+#pragma unroll
+    for (int g = 0; g < UW; ++g) acc[g] = b0;
+    if constexpr (Shared) {
+      for (int f0 = 0; f0 < a.k; f0 += RC_KC) {
+        const int kc = a.k - f0 < RC_KC ? a.k - f0 : RC_KC;
+        __syncthreads();
+        // row r of the tile is lane r's candidate; a wave stages 64 columns of one row at a time
+        for (int r = w; r < RC_TI; r += RC_W) {
+          const int32_t ri = __shfl(item, r, 64);
+          tile[r * RC_TS + lane] =
+              (p0 + r < c1 && lane < kc) ? a.I[(int64_t)ri * a.kp + f0 + lane] : (T)0;
+        }
+        __syncthreads();
+        const T* q = &tile[lane * RC_TS];
+        const cdptr u0 = ud + f0 * RC_UW;
+        if (kc == RC_KC) {
+#pragma unroll
+          for (int f = 0; f < RC_KC; ++f) {
+            const double qf = (double)q[f];
+#pragma unroll
+            for (int g = 0; g < UW; ++g) acc[g] = mul_add_rn(acc[g], u0[f * RC_UW + g], qf);
+          }
+        } else {
+          for (int f = 0; f < kc; ++f) {
+            const double qf = (double)q[f];
+#pragma unroll
+            for (int g = 0; g < UW; ++g) acc[g] = mul_add_rn(acc[g], u0[f * RC_UW + g], qf);
+          }
+        }
+      }
+    } else {
+      // eight loads of the lane's own row in flight; kp is a multiple of 16, so they stay
+      // inside the row
+      const T* row = a.I + (int64_t)item * a.kp;
+      for (int f0 = 0; f0 < a.k; f0 += 8) {
+        T v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = row[f0 + j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (f0 + j < a.k) acc[0] = mul_add_rn(acc[0], ud[(f0 + j) * RC_UW], (double)v[j]);
+      }
+    }
+
+    // proposals: listed, ranking before the user's threshold and unseen
+#pragma unroll
+    for (int g = 0; g < UW; ++g) {
+      if (tw + g >= a.nreq) break;  // uniform over the wave
+      const int u = w * UW + g;
+      const int cnt = uniform(st_cnt[u]);
+      const int32_t thi = st_thi[u];
+      const double ths = st_thr[u];
+      bool propose = valid && (thi < 0 || rec_before(acc[g], item, ths, thi));
+      if (a.seen_ptr) {
+        const int64_t urow = uniform(a.users[tw + g]);
+        const int64_t lo = uniform(a.seen_ptr[urow]), end = uniform(a.seen_ptr[urow + 1]);
+        if (propose) propose = !cand_seen(a.seen_col, lo, end, item);
+      }
+      const RecList L{cand_s + u * RC_CAP, cand_i + u * RC_CAP};
+      const int n = rec_append(L, cnt, propose, acc[g], item);
+      if (lane == 0) st_cnt[u] = n;
+    }
+
+    // as in rec_select_kernel: prune a list that could not take another tile or holds N
+    // without a threshold; a full list's last entry is the new threshold
+    for (int g = 0; g < UW; ++g) {
+      const int u = w * UW + g;
+      const int cnt = uniform(st_cnt[u]);
+      const int thi = uniform(st_thi[u]);
+      if (cnt > RC_CAP - RC_TI || (thi < 0 && cnt >= a.topn)) {
+        const RecList L{cand_s + u * RC_CAP, cand_i + u * RC_CAP};
+        const int n = rec_prune(L, cnt, a.topn, lane);
+        if (lane == 0) {
+          st_cnt[u] = n;
+          if (n == a.topn) {
+            st_thr[u] = L.s[n - 1];
+            st_thi[u] = L.i[n - 1];
+          }
+        }
+      }
+    }
+  }
+
+  // the chunk's survivors in rank order → the partial list of every user
+  for (int g = 0; g < UW; ++g) {
+    if (tw + g >= a.nreq) break;
+    const int u = w * UW + g;
+    const RecList L{cand_s + u * RC_CAP, cand_i + u * RC_CAP};
+    const int n = rec_prune(L, uniform(st_cnt[u]), a.topn, lane);
+    const int64_t slot = slot0 + g;
+    for (int j = lane; j < n; j += 64) {
+      a.part_score[slot * a.topn + j] = L.s[j];
+      a.part_item[slot * a.topn + j] = L.i[j];
+    }
+    if (lane == 0) a.part_cnt[slot] = n;
+  }
+}
+
+template <typename T>
+hipError_t select_candidates(const CandArgs<T>& a0, hipStream_t s) {
+  if (a0.k > RC_KMAX || a0.topn < 1 || a0.topn > kRecMaxN) return hipErrorInvalidValue;
+  if (a0.nreq == 0) return hipSuccess;
+  CandArgs<T> a = a0;
+  hipError_t e = hipFuncSetAttribute((const void*)cand_select_kernel<T, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     CandShape<true>::lds_bytes<T>());
+  if (e != hipSuccess) return e;
+  const bool shared = a.cptr == nullptr;
+  const int64_t groups = (a.nreq + RC_UG - 1) / RC_UG;
+  const int64_t nchunk = shared ? cand_chunks(a.ncand) : 0;
+  // users in batches, as select() takes them
+  const int64_t bg = eval_batch_groups();
+  for (int64_t g0 = 0; g0 < groups; g0 += bg) {
+    const int64_t ng = groups - g0 < bg ? groups - g0 : bg;
+    a.t_base = g0 * RC_UG;
+    a.nbatch = ng * RC_UG;
+    const int64_t nu = a.nreq - a.t_base < a.nbatch ? a.nreq - a.t_base : a.nbatch;
+    hipLaunchKernelGGL(rec_users_kernel<T>, dim3((unsigned)a.nbatch), dim3(256), 0, s,
+                       static_cast<const RecArgs<T>&>(a));
+    if (shared) {
+      if (nchunk > 0)
+        hipLaunchKernelGGL((cand_select_kernel<T, true>), dim3((unsigned)nchunk, (unsigned)ng),
+                           dim3(256), CandShape<true>::lds_bytes<T>(), s, a);
+    } else {
+      a.w_base = a.h_woff[a.t_base];
+      a.w_end = a.h_woff[a.t_base + nu];
+      const int64_t nwg = (a.w_end - a.w_base + RC_W - 1) / RC_W;
+      if (nwg > 0)
+        hipLaunchKernelGGL((cand_select_kernel<T, false>), dim3((unsigned)nwg), dim3(256),
+                           CandShape<false>::lds_bytes<T>(), s, a);
+    }
+    const RecMergeArgs m{a.part_score, a.part_item, a.part_cnt, nchunk,   a.nbatch, a.t_base,
+                         a.nreq,       a.topn,      a.items,    a.scores, a.counts,
+                         shared ? nullptr : a.woff};
     hipLaunchKernelGGL(rec_merge_kernel, dim3((unsigned)nu), dim3(64), 0, s, m);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -483,10 +746,17 @@ hipError_t factor_norms(const T* F, int64_t n, int k, int kp, double* norms, hip
 }  // namespace
 
 hipError_t launch_recommend(const RecArgs<float>& a, hipStream_t s) {
-  return select<float, SEL_RECOMMEND>(a, s);
+  return a.deny ? select<float, SEL_RECOMMEND_DENY>(a, s) : select<float, SEL_RECOMMEND>(a, s);
 }
 hipError_t launch_recommend(const RecArgs<double>& a, hipStream_t s) {
-  return select<double, SEL_RECOMMEND>(a, s);
+  return a.deny ? select<double, SEL_RECOMMEND_DENY>(a, s) : select<double, SEL_RECOMMEND>(a, s);
+}
+int64_t cand_chunks(int64_t n) { return (n + RC_CHUNK - 1) / RC_CHUNK; }
+hipError_t launch_recommend_candidates(const CandArgs<float>& a, hipStream_t s) {
+  return select_candidates(a, s);
+}
+hipError_t launch_recommend_candidates(const CandArgs<double>& a, hipStream_t s) {
+  return select_candidates(a, s);
 }
 hipError_t launch_similar(const SimArgs<float>& a, hipStream_t s) { return similar(a, s); }
 hipError_t launch_similar(const SimArgs<double>& a, hipStream_t s) { return similar(a, s); }

@@ -285,13 +285,87 @@ void savePairs(const IdIndex& queryIndex, const IdIndex& otherIndex,
 
 }  // namespace
 
+namespace {
+
+std::vector<int64_t> sortedUnique(std::vector<int64_t> v) {
+  std::sort(v.begin(), v.end());
+  v.erase(std::unique(v.begin(), v.end()), v.end());
+  return v;
+}
+
+}  // namespace
+
 void Engine::saveRecommendations(qmfx_ctx* ctx, const int exclude, const bool useBiases,
                                  const IdIndex& userIndex, const IdIndex& itemIndex,
                                  const std::string& fileName, const size_t topN,
-                                 const std::vector<int64_t>* userIds, const AfterBatch* after) {
+                                 const std::vector<int64_t>* userIds, const AfterBatch* after,
+                                 const RecommendScope& scope) {
   CHECK(topN >= 1 && topN <= QMFX_REC_MAX_N)
       << "the number of recommendations must be in 1.." << QMFX_REC_MAX_N << ", got " << topN;
+  CHECK((scope.excludeItemIds != nullptr) + (scope.itemIds != nullptr) +
+            (scope.candidates != nullptr) <= 1)
+      << "a recommendation scope sets at most one of its lists";
+  const int n = static_cast<int>(topN), biases = useBiases ? 1 : 0;
+  if (scope.candidates) {
+    CHECK(!userIds) << "per-user candidates name their own users";
+    // the known (user idx, item idx) pairs, ascending and distinct: users with their lists
+    std::vector<std::pair<int64_t, int64_t>> pairs;
+    size_t unknown = 0;
+    for (const auto& e : *scope.candidates) {
+      const size_t u = userIndex.idx(e.userId), i = itemIndex.idx(e.itemId);
+      if (u == IdIndex::missingIdx || i == IdIndex::missingIdx)
+        ++unknown;
+      else
+        pairs.emplace_back(static_cast<int64_t>(u), static_cast<int64_t>(i));
+    }
+    if (unknown > 0)
+      LOG(WARNING) << unknown << " candidate lines name a user or item id that is not in the "
+                   << "training data; skipped";
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    std::vector<int64_t> users, cptr(1, 0), cand;
+    for (const auto& p : pairs) {
+      if (users.empty() || users.back() != p.first) {
+        users.push_back(p.first);
+        cptr.push_back(cptr.back());
+      }
+      cand.push_back(p.second);
+      ++cptr.back();
+    }
+    std::vector<int64_t> bptr;  // a batch's offsets, from 0
+    savePairs(userIndex, itemIndex, users, fileName, topN,
+              [&](const int64_t* rows, const size_t nr, int64_t* items, double* scores,
+                  int32_t* counts) {
+                const int64_t* p = cptr.data() + (rows - users.data());
+                bptr.assign(p, p + nr + 1);
+                for (auto& b : bptr) b -= p[0];
+                QMFX_CHECK(qmfx_recommend_candidates(ctx, static_cast<int64_t>(nr), rows,
+                                                     bptr.data(), 0, cand.data() + p[0], n,
+                                                     exclude, biases, items, scores, counts));
+              },
+              after);
+    return;
+  }
   const std::vector<int64_t> users = queryRows(userIndex, userIds, "user");
+  if (scope.excludeItemIds || scope.itemIds) {
+    const bool deny = scope.excludeItemIds != nullptr;
+    const std::vector<int64_t> list =
+        sortedUnique(queryRows(itemIndex, deny ? scope.excludeItemIds : scope.itemIds, "item"));
+    const int64_t nl = static_cast<int64_t>(list.size());
+    savePairs(userIndex, itemIndex, users, fileName, topN,
+              [&](const int64_t* rows, const size_t nr, int64_t* items, double* scores,
+                  int32_t* counts) {
+                const int64_t nu = static_cast<int64_t>(nr);
+                if (deny)
+                  QMFX_CHECK(qmfx_recommend_without(ctx, nu, rows, nl, list.data(), n, exclude,
+                                                    biases, items, scores, counts));
+                else
+                  QMFX_CHECK(qmfx_recommend_candidates(ctx, nu, rows, nullptr, nl, list.data(), n,
+                                                       exclude, biases, items, scores, counts));
+              },
+              after);
+    return;
+  }
   savePairs(userIndex, itemIndex, users, fileName, topN,
             [&](const int64_t* rows, const size_t n, int64_t* items, double* scores,
                 int32_t* counts) {

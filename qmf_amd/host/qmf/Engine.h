@@ -17,6 +17,19 @@
 
 namespace qmf {
 
+// Which items a saveUserRecommendations call may recommend; at most one member is set (none:
+// every item).  Ids the model does not know are skipped with one warning carrying their count.
+struct RecommendScope {
+  // item ids that are never recommended (include/qmfx.h qmfx_recommend_without)
+  const std::vector<int64_t>* excludeItemIds = nullptr;
+  // the only item ids that are recommended, to every user (qmfx_recommend_candidates, shared list)
+  const std::vector<int64_t>* itemIds = nullptr;
+  // per-user candidates as dataset lines (the value is ignored): a user is recommended only the
+  // items listed with them, and the requested users are exactly the lines' known users, in
+  // ascending user idx; excludes userIds
+  const std::vector<DatasetElem>* candidates = nullptr;
+};
+
 class Engine {
  public:
   Engine() = default;
@@ -38,9 +51,10 @@ class Engine {
   // "<userId> <itemId> <score>\n" per pair, scores with 9 decimals, each user's lines in rank
   // order (higher score first, equal scores by ascending item idx): the dataset format, so
   // DatasetReader reads the file back.  includeSeen = false leaves the user's training items
-  // out; a user with no eligible item writes nothing.
+  // out; a user with no eligible item writes nothing.  `scope` narrows the eligible items.
   virtual void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
-                                       const std::vector<int64_t>* userIds = nullptr) const {}
+                                       const std::vector<int64_t>* userIds = nullptr,
+                                       const RecommendScope& scope = RecommendScope()) const {}
   // Addition to the reference API: the topN (1..QMFX_REC_MAX_N) nearest items of every item
   // (ascending item idx), or of the items in `itemIds` in that order (unknown ids are skipped
   // with one warning), among the items, by cosine (else by dot product) of the current factors,
@@ -82,12 +96,15 @@ class Engine {
  protected:
   // saveUserRecommendations of the engines: qmfx_recommend (include/qmfx.h) with the given
   // exclude mode in batches of at most 65,536 users, formatted and written batch by batch;
-  // `after` (unless null) sees every batch's lists once they are selected
+  // `after` (unless null) sees every batch's lists once they are selected.  With a scope the
+  // batches go to qmfx_recommend_without / qmfx_recommend_candidates, the item lists sorted and
+  // deduplicated here.
   static void saveRecommendations(qmfx_ctx* ctx, int exclude, bool useBiases,
                                   const IdIndex& userIndex, const IdIndex& itemIndex,
                                   const std::string& fileName, size_t topN,
                                   const std::vector<int64_t>* userIds,
-                                  const AfterBatch* after = nullptr);
+                                  const AfterBatch* after = nullptr,
+                                  const RecommendScope& scope = RecommendScope());
 
   // formatExplanations of all the pairs, in blocks in parallel, written to `out` in order
   static void writeExplanations(const IdIndex& queryIndex, const IdIndex& otherIndex,

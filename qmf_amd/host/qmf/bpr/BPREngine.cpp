@@ -225,11 +225,13 @@ void BPREngine::saveItemFactors(const std::string& fileName) const {
 
 void BPREngine::saveUserRecommendations(const std::string& fileName, const size_t topN,
                                         const bool includeSeen,
-                                        const std::vector<int64_t>* userIds) const {
+                                        const std::vector<int64_t>* userIds,
+                                        const RecommendScope& scope) const {
   CHECK(dev_) << "no factor data, have you initialized the engine?";
   CHECK_EQ(deviceOptions_.ngpus, 1) << "recommendations need --ngpus=1";
   saveRecommendations(dev_->get(), includeSeen ? QMFX_REC_ALL : QMFX_REC_UNSEEN_POSITIVES,
-                      config_.useBiases, userIndex_, itemIndex_, fileName, topN, userIds);
+                      config_.useBiases, userIndex_, itemIndex_, fileName, topN, userIds, nullptr,
+                      scope);
 }
 
 void BPREngine::saveItemSimilarities(const std::string& fileName, const size_t topN,

@@ -62,7 +62,8 @@ class BPREngine : public Engine {
   // includeSeen = false leaves out the user's training positives; scores include the item
   // biases when the model uses them
   void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
-                               const std::vector<int64_t>* userIds = nullptr) const override;
+                               const std::vector<int64_t>* userIds = nullptr,
+                               const RecommendScope& scope = RecommendScope()) const override;
   // the query itself is always left out; item biases are never part of a similarity
   void saveItemSimilarities(const std::string& fileName, size_t topN, bool cosine,
                             const std::vector<int64_t>* itemIds = nullptr) const override;

@@ -184,12 +184,13 @@ void WALSEngine::saveItemFactors(const std::string& fileName) const {
 
 void WALSEngine::saveUserRecommendations(const std::string& fileName, const size_t topN,
                                          const bool includeSeen,
-                                         const std::vector<int64_t>* userIds) const {
+                                         const std::vector<int64_t>* userIds,
+                                         const RecommendScope& scope) const {
   CHECK(dev_) << "no factor data, have you initialized the engine?";
   // a rank holds only its own users' signals; routing users to their rank is not built
   CHECK_EQ(ranks_.size(), 1u) << "recommendations need --ngpus=1";
   saveRecommendations(dev_->get(), includeSeen ? QMFX_REC_ALL : QMFX_REC_UNSEEN_SIGNALS, false,
-                      userIndex_, itemIndex_, fileName, topN, userIds);
+                      userIndex_, itemIndex_, fileName, topN, userIds, nullptr, scope);
 }
 
 namespace {
@@ -226,7 +227,8 @@ void WALSEngine::saveRecommendationExplanations(const std::string& recommendatio
                                                 const std::string& explanationsFile,
                                                 const size_t topN, const size_t topM,
                                                 const bool includeSeen,
-                                                const std::vector<int64_t>* userIds) const {
+                                                const std::vector<int64_t>* userIds,
+                                                const RecommendScope& scope) const {
   CHECK(dev_) << "no factor data, have you initialized the engine?";
   CHECK_EQ(ranks_.size(), 1u) << "recommendations need --ngpus=1";
   CHECK(topM >= 1 && topM <= QMFX_REC_MAX_N)
@@ -248,7 +250,7 @@ void WALSEngine::saveRecommendationExplanations(const std::string& recommendatio
                       x.contribs.data(), x.counts.data(), eout);
   };
   saveRecommendations(c, includeSeen ? QMFX_REC_ALL : QMFX_REC_UNSEEN_SIGNALS, false, userIndex_,
-                      itemIndex_, recommendationsFile, topN, userIds, &after);
+                      itemIndex_, recommendationsFile, topN, userIds, &after, scope);
 }
 
 void WALSEngine::saveItemSimilarities(const std::string& fileName, const size_t topN,

@@ -52,7 +52,8 @@ class WALSEngine : public Engine {
   void saveItemFactors(const std::string& fileName) const override;
   // includeSeen = false leaves out the items of the user's training signals (one GPU only)
   void saveUserRecommendations(const std::string& fileName, size_t topN, bool includeSeen,
-                               const std::vector<int64_t>* userIds = nullptr) const override;
+                               const std::vector<int64_t>* userIds = nullptr,
+                               const RecommendScope& scope = RecommendScope()) const override;
   // saveUserRecommendations to recommendationsFile, and to explanationsFile why: for every
   // (user, item) pair of that file, in its order, the topM (1..QMFX_REC_MAX_N) training signals
   // of the user that contribute most to y_itemᵀA_u⁻¹b_u (include/qmfx.h qmfx_wals_explain, the
@@ -64,7 +65,8 @@ class WALSEngine : public Engine {
   void saveRecommendationExplanations(const std::string& recommendationsFile,
                                       const std::string& explanationsFile, size_t topN,
                                       size_t topM, bool includeSeen,
-                                      const std::vector<int64_t>* userIds = nullptr) const;
+                                      const std::vector<int64_t>* userIds = nullptr,
+                                      const RecommendScope& scope = RecommendScope()) const;
   // the query itself is always left out; with several GPUs rank 0 answers (full replicas)
   void saveItemSimilarities(const std::string& fileName, size_t topN, bool cosine,
                             const std::vector<int64_t>* itemIds = nullptr) const override;

@@ -1,8 +1,10 @@
 // `wals` command line, drop-in for the reference's qmf/wals.cpp:26-107: same flags, same
 // log lines and output files.  Additions: --device, --precision (32 | 64), --ngpus, and the
 // top-N recommendations of the trained model: --user_recommendations, --num_recommendations,
-// --recommend_seen, --recommend_users; and the items' / users' nearest neighbours in factor
-// space: --item_similarities, --user_similarities, --num_similar, --similarity,
+// --recommend_seen, --recommend_users, and one of --recommend_exclude_items FILE (item ids never
+// recommended), --recommend_items FILE (the only item ids recommended) or
+// --recommend_candidates FILE ("user item weight" lines: these users, each only from the items
+// listed with them); and the items' / users' nearest neighbours in factor space: --item_similarities, --user_similarities, --num_similar, --similarity,
 // --similar_item_ids, --similar_user_ids; and fold-in of users the model was not trained on:
 // --fold_in_dataset FILE ("user item weight" lines, the training format; its users are solved
 // as new rows against the trained item factors even if their id was trained, and lines naming
@@ -61,6 +63,13 @@ DEFINE_uint64(num_recommendations, 10, "items recommended per user (1..128)");
 DEFINE_bool(recommend_seen, false, "also recommend items of the user's training data");
 DEFINE_string(recommend_users, "",
               "file with one user id per line to recommend for (default: every training user)");
+DEFINE_string(recommend_exclude_items, "",
+              "file with one item id per line that is never recommended");
+DEFINE_string(recommend_items, "",
+              "file with one item id per line: recommendations come only from these items");
+DEFINE_string(recommend_candidates, "",
+              "file of 'user item weight' lines (the training format, the weight is ignored): "
+              "recommend to exactly these users, each only from the items listed with them");
 // similar items / users (nearest neighbours in factor space)
 DEFINE_string(item_similarities, "", "filename of the items' top-N most similar items");
 DEFINE_string(user_similarities, "", "filename of the users' top-N most similar users");
@@ -121,6 +130,18 @@ int main(int argc, char** argv) {
   if (!FLAGS_user_recommendations.empty() || !FLAGS_fold_in_recommendations.empty())
     CHECK(FLAGS_num_recommendations >= 1 && FLAGS_num_recommendations <= QMFX_REC_MAX_N)
         << "--num_recommendations must be in 1.." << QMFX_REC_MAX_N;
+  {
+    // what may be recommended: at most one of the three scope flags, on --user_recommendations
+    const int scopes = !FLAGS_recommend_exclude_items.empty() + !FLAGS_recommend_items.empty() +
+                       !FLAGS_recommend_candidates.empty();
+    CHECK(scopes <= 1) << "--recommend_exclude_items, --recommend_items and "
+                          "--recommend_candidates are mutually exclusive";
+    CHECK(FLAGS_recommend_candidates.empty() || FLAGS_recommend_users.empty())
+        << "--recommend_candidates and --recommend_users are mutually exclusive";
+    CHECK(scopes == 0 || !FLAGS_user_recommendations.empty())
+        << "--recommend_exclude_items, --recommend_items and --recommend_candidates need "
+           "--user_recommendations";
+  }
   if (!FLAGS_recommendation_explanations.empty())
     CHECK(!FLAGS_user_recommendations.empty())
         << "--recommendation_explanations needs --user_recommendations";
@@ -177,13 +198,28 @@ int main(int argc, char** argv) {
     std::vector<int64_t> ids;
     if (!FLAGS_recommend_users.empty()) ids = qmf::readIds(FLAGS_recommend_users);
     const std::vector<int64_t>* users = FLAGS_recommend_users.empty() ? nullptr : &ids;
+    // the scope flags' files, read into the scope of the save call
+    std::vector<int64_t> scopeIds;
+    std::vector<qmf::DatasetElem> scopeLines;
+    qmf::RecommendScope scope;
+    if (!FLAGS_recommend_exclude_items.empty()) {
+      scopeIds = qmf::readIds(FLAGS_recommend_exclude_items);
+      scope.excludeItemIds = &scopeIds;
+    } else if (!FLAGS_recommend_items.empty()) {
+      scopeIds = qmf::readIds(FLAGS_recommend_items);
+      scope.itemIds = &scopeIds;
+    } else if (!FLAGS_recommend_candidates.empty()) {
+      qmf::DatasetReader candReader(FLAGS_recommend_candidates);
+      scopeLines = candReader.readAll();
+      scope.candidates = &scopeLines;
+    }
     if (FLAGS_recommendation_explanations.empty())
       engine.saveUserRecommendations(FLAGS_user_recommendations, FLAGS_num_recommendations,
-                                     FLAGS_recommend_seen, users);
+                                     FLAGS_recommend_seen, users, scope);
     else
       engine.saveRecommendationExplanations(
           FLAGS_user_recommendations, FLAGS_recommendation_explanations,
-          FLAGS_num_recommendations, FLAGS_num_explanations, FLAGS_recommend_seen, users);
+          FLAGS_num_recommendations, FLAGS_num_explanations, FLAGS_recommend_seen, users, scope);
     if (timings())
       LOG(INFO) << "timing: recommend " << now() - t0 << " s, "
                 << fileBytes(FLAGS_user_recommendations) << " bytes";
