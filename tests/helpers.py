@@ -104,11 +104,13 @@ def ladder_case(k, seed, precision, with_empty=True):
     return out
 
 
-def ladder_reference(rowptr, col, val, Y, alpha, lam):
+def ladder_reference(rowptr, col, val, Y, alpha, lam, with_cond=True):
     """Plain numpy fp64, row by row: A = YᵀY + Yᵣᵀ·diag(αv)·Yᵣ + λI, b = Yᵣᵀ(1 + αv),
     x = solve(A, b), loss = Σc + xᵀ(A − λI)x − 2xᵀb (include/qmfx.h).  Returns
     (X, loss, cond₂(A), S) per row, S = Σc + |xᵀ(A − λI)x| + 2|xᵀb| (the size of the loss's
-    terms: what a loss error is measured against)."""
+    terms: what a loss error is measured against).  `with_cond=False` skips the per-row
+    eigenvalues (the larger part of the cost at k = 256) and returns NaN for cond₂: for callers
+    whose bound does not use it."""
     Y = np.asarray(Y, np.float64)
     k = Y.shape[1]
     G = Y.T @ Y
@@ -127,8 +129,11 @@ def ladder_reference(rowptr, col, val, Y, alpha, lam):
         X[r] = x
         loss[r] = cs + quad - 2.0 * xb
         S[r] = cs + abs(quad) + 2.0 * abs(xb)
-        ev = np.linalg.eigvalsh(A)  # A is symmetric positive definite: cond₂ = λmax / λmin
-        cond[r] = ev[-1] / ev[0]
+        if with_cond:
+            ev = np.linalg.eigvalsh(A)  # A is symmetric positive definite: cond₂ = λmax / λmin
+            cond[r] = ev[-1] / ev[0]
+        else:
+            cond[r] = np.nan
     return X, loss, cond, S
 
 
@@ -213,6 +218,81 @@ def signed_ladder_solution(k, seed, precision, recipe, alpha, lam):
     for a in out:
         a.setflags(write=False)
     return out
+
+
+# ---- the fixed-side stages of a half (tests/test_fixed_side_gpu.py): problems in which every
+# row of both sides is whitened and L⁻¹ of YᵀY + λI is far from a multiple of I
+FIXED_LADDER = (1, 2, 3, 5, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 127, 128, 129, 255,
+                256, 257, 511, 512, 513, 1023, 1024, 1025)
+FIXED_ALPHA, FIXED_LAM = 1.0, 0.05
+
+
+@functools.lru_cache(maxsize=None)
+def mixing_matrix(k):
+    """A fixed seeded k×k matrix U·diag(s)·Vᵀ (U, V orthogonal) whose singular values s fall
+    geometrically from 1 to 0.1."""
+    rng = np.random.default_rng(7000 + k)
+    U = np.linalg.qr(rng.standard_normal((k, k)))[0]
+    V = np.linalg.qr(rng.standard_normal((k, k)))[0]
+    s = 10.0 ** (-np.arange(k) / max(k - 1, 1))
+    out = (U * s) @ V.T
+    out.setflags(write=False)
+    return out
+
+
+def correlated_factors(n, k, seed, precision):
+    """n×k factors R·C, R uniform(−1, 1) and C = mixing_matrix(k), scaled to ‖·‖₂ = 1 and, for
+    precision 32, rounded to fp32 (then widened).  The columns are correlated, so the Cholesky
+    factor of YᵀY + λI at λ = 0.05 has off-diagonal entries of the size of its diagonal."""
+    rng = np.random.default_rng(seed)
+    Y = rng.uniform(-1.0, 1.0, (n, k)) @ mixing_matrix(k)
+    Y /= np.linalg.norm(Y, 2)
+    if precision == 32:
+        Y = Y.astype(np.float32).astype(np.float64)
+    return Y
+
+
+@functools.lru_cache(maxsize=64)
+def fixed_side_case(m, n, k, precision):
+    """((urp, ucol, uval), (irp, icol, ival), (X, Y)) for m users and n items: the signals
+    (u, u mod n), (u, (u + 1) mod n), (u, (u + 7) mod n) of every user and (i mod m, i) of every
+    item, de-duplicated, so that no row of either side is empty and every row of either side's
+    factors is gathered by a row of the other; with max(m, n) / min(m, n) ≤ 4 no row has more
+    than 16 signals.  Values uniform(0.05, 1]; X and Y are correlated_factors of m and n rows.
+    precision 32 rounds values and factors to fp32 first.  Cached (the last 64): read-only."""
+    u, i = np.arange(m, dtype=np.int64), np.arange(n, dtype=np.int64)
+    users = np.concatenate([u, u, u, i % m])
+    items = np.concatenate([u % n, (u + 1) % n, (u + 7) % n, i])
+    keys = np.unique(users * n + items)
+    users, items = keys // n, keys % n
+    seed = (m * 2048 + n) * 512 + k
+    values = 1.0 - np.random.default_rng(seed).uniform(0.0, 0.95, len(keys))
+    if precision == 32:
+        values = values.astype(np.float32).astype(np.float64)
+    _, _, ucsr, icsr = csr_from_triples(users, items, values)
+    F = (correlated_factors(m, k, seed + 1, precision), correlated_factors(n, k, seed + 2, precision))
+    for a in (*ucsr, *icsr, *F):
+        a.setflags(write=False)
+    return ucsr, icsr, F
+
+
+@functools.lru_cache(maxsize=64)
+def fixed_side_solution(m, n, k, precision, side):
+    """ladder_reference of the half that solves `side` of fixed_side_case(m, n, k, precision)
+    against the other side's factors at (FIXED_ALPHA, FIXED_LAM), and the largest off-diagonal
+    magnitude of numpy's L⁻¹ (L Lᵀ = FᵀF + λI of the fixed side) over its largest diagonal
+    entry.  cond₂ per row only for precision 32 (the fp64 bound does not use it).  Cached (the
+    last 64): read-only."""
+    ucsr, icsr, F = fixed_side_case(m, n, k, precision)
+    fixed = F[1 - side]
+    out = ladder_reference(*(ucsr, icsr)[side], fixed, FIXED_ALPHA, FIXED_LAM,
+                           with_cond=precision == 32)
+    Linv = np.linalg.inv(np.linalg.cholesky(fixed.T @ fixed + FIXED_LAM * np.eye(k)))
+    d = np.abs(np.diag(Linv))
+    ratio = float(np.max(np.abs(Linv) - np.diag(d)) / d.max())
+    for a in out:
+        a.setflags(write=False)
+    return (*out, ratio)
 
 
 # ---- restatement of the BPR epoch's visiting order and negative draws (qmf_amd/csrc/bpr.hip
