@@ -6,6 +6,8 @@
 // (WALSEngine.cpp:130-163); here, for data generated on the device, the same "sort by
 // (row id, col id), group by row" is a radix sort of 64-bit keys followed by a
 // lower-bound per row.  Row and column indices are the ids, so id ordering is preserved.
+#include <algorithm>
+
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
@@ -179,7 +181,10 @@ hipError_t launch_fill_uniform(double* X, int64_t n, int kp, int k, double bound
 }
 
 // Radix sort of 64-bit keys (in place via a scratch buffer of equal size) and in-place
-// unique; *n_out receives the unique count.  `scratch` must hold n keys.
+// unique; *n_out receives the unique count.  `scratch` must hold n keys.  The temporary
+// storage is an allocation of its own (hipMalloc, as ingest.hip's), released after the
+// stream has drained: a block of the stream-ordered pool, taken again on the same stream by a
+// later and larger call, gave a count of 0 or a lookback that never ended.
 hipError_t sort_unique_keys(uint64_t* keys, uint64_t* scratch, int64_t n, int64_t* n_out,
                             int end_bit, hipStream_t s) {
   size_t tmp_sort = 0, tmp_uniq = 0;
@@ -190,17 +195,16 @@ hipError_t sort_unique_keys(uint64_t* keys, uint64_t* scratch, int64_t n, int64_
   int64_t* d_num = nullptr;
   e = hipcub::DeviceSelect::Unique(nullptr, tmp_uniq, scratch, keys, d_num, (int)n, s);
   if (e != hipSuccess) return e;
-  const size_t tmp = tmp_sort > tmp_uniq ? tmp_sort : tmp_uniq;
-  void* d_tmp = nullptr;
-  const size_t num_off = (tmp + 15) & ~(size_t)15;
-  if ((e = hipMallocAsync(&d_tmp, num_off + 64, s)) != hipSuccess) return e;
-  d_num = (int64_t*)((char*)d_tmp + num_off);
+  DevPtr<void> d_tmp;
+  DevPtr<int64_t> num;
+  if ((e = dev_alloc(d_tmp, std::max<size_t>(std::max(tmp_sort, tmp_uniq), 16))) != hipSuccess) return e;
+  if ((e = dev_alloc(num, sizeof(int64_t))) != hipSuccess) return e;
+  d_num = num;
   e = hipcub::DeviceRadixSort::SortKeys(d_tmp, tmp_sort, keys, scratch, (int)n, 0, end_bit, s);
   if (e == hipSuccess) e = hipcub::DeviceSelect::Unique(d_tmp, tmp_uniq, scratch, keys, d_num, (int)n, s);
   if (e == hipSuccess) e = hipMemcpyAsync(n_out, d_num, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFreeAsync(d_tmp, s);
-  return e;
+  const hipError_t es = hipStreamSynchronize(s);  // before d_tmp and num go, on every path
+  return e != hipSuccess ? e : es;
 }
 
 // Stable sort of keys only (for the transposed orientation; keys are unique already).
@@ -209,12 +213,12 @@ hipError_t sort_keys(uint64_t* keys, uint64_t* scratch, int64_t n, int end_bit, 
   size_t tmp = 0;
   hipError_t e = hipcub::DeviceRadixSort::SortKeys(nullptr, tmp, keys, scratch, (int)n, 0, end_bit, s);
   if (e != hipSuccess) return e;
-  void* d_tmp = nullptr;
-  if ((e = hipMallocAsync(&d_tmp, tmp + 16, s)) != hipSuccess) return e;
+  DevPtr<void> d_tmp;
+  if ((e = dev_alloc(d_tmp, std::max<size_t>(tmp, 16))) != hipSuccess) return e;
   e = hipcub::DeviceRadixSort::SortKeys(d_tmp, tmp, keys, scratch, (int)n, 0, end_bit, s);
   if (e == hipSuccess) e = hipMemcpyAsync(keys, scratch, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, s);
-  (void)hipFreeAsync(d_tmp, s);
-  return e;
+  const hipError_t es = hipStreamSynchronize(s);  // before d_tmp goes
+  return e != hipSuccess ? e : es;
 }
 
 }  // namespace qmfx

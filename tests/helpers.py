@@ -436,3 +436,179 @@ def eval_chunks(ntest, nitems):
     chunk = -(-(-(-nitems // n)) // 64) * 64
     n = -(-nitems // chunk)
     return n, -(-(-(-nitems // n)) // 64) * 64
+
+
+# ---- the device's synthetic data (qmf_amd/csrc/data.hip and the driver qmfx_gen_synthetic_zipf
+# in api_signals.cpp) and qmfx_fill_uniform, restated in numpy uint64 arithmetic (which wraps
+# mod 2⁶⁴ as the device's does).  tests/test_synth.py anchors each piece on Python integers;
+# tests/test_synth_gpu.py compares the device with them bit for bit.
+_U = np.uint64
+
+
+def mix64_np(x):
+    """mix64 over a uint64 array."""
+    x = np.asarray(x, _U) + _U(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> _U(30))) * _U(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> _U(27))) * _U(0x94D049BB133111EB)
+    return x ^ (x >> _U(31))
+
+
+def mulhi64_np(a, b):
+    """The high 64 bits of the 128-bit product a·b, a a uint64 array and b one integer < 2⁶⁴,
+    from 32-bit limbs (no partial sum reaches 2⁶⁴)."""
+    a = np.asarray(a, _U)
+    lo32, s32 = _U(M32), _U(32)
+    a0, a1 = a & lo32, a >> s32
+    b0, b1 = _U(int(b) & M32), _U(int(b) >> 32)
+    ll, hl, lh, hh = a0 * b0, a1 * b0, a0 * b1, a1 * b1
+    cross = (ll >> s32) + (hl & lo32) + (lh & lo32)
+    return hh + (hl >> s32) + (lh >> s32) + (cross >> s32)
+
+
+def _csr_pair(ukeys, nusers, nitems, seed):
+    """Both CSR orientations of the pairs whose sorted distinct user-major keys u·nitems + i are
+    `ukeys` (uint64): ((urp, ucol, uval), (irp, icol, ival)).  The value of (u, i) in both is
+    1 + mix64((seed·31 + 7 mod 2⁶⁴) ^ (u·nitems + i)) % 5; the item side is the transposed keys
+    i·nusers + u, sorted."""
+    vseed = _U((int(seed) * 31 + 7) & M64)
+
+    def values(u, i):
+        return (_U(1) + mix64_np(vseed ^ (u * _U(nitems) + i)) % _U(5)).astype(np.float64)
+
+    def side(keys, nrows, ncols):
+        rows, cols = keys // _U(ncols), keys % _U(ncols)
+        counts = np.bincount(rows.astype(np.int64), minlength=nrows)
+        return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), rows, cols
+
+    urp, u, i = side(ukeys, nusers, nitems)
+    ucsr = (urp, i.astype(np.int32), values(u, i))
+    irp, it, us = side(np.sort(i * _U(nusers) + u), nitems, nusers)
+    icsr = (irp, us.astype(np.int32), values(us, it))
+    for a in (*ucsr, *icsr):
+        a.setflags(write=False)
+    return ucsr, icsr
+
+
+@functools.lru_cache(maxsize=None)
+def synth_reference(nusers, nitems, nnz, seed):
+    """What qmfx_gen_synthetic(nusers, nitems, nnz, seed) leaves in a context:
+    (m, (urp, ucol, uval), (irp, icol, ival)).  Draw i's key is
+    (mix64(seed ^ mix64(i)) · space) >> 64 with space = nusers·nitems; the kept pairs are the
+    m sorted distinct keys.  Cached: the arrays are read-only."""
+    h = mix64_np(_U(seed) ^ mix64_np(np.arange(nnz, dtype=_U)))
+    keys = np.unique(mulhi64_np(h, nusers * nitems))
+    return (len(keys), *_csr_pair(keys, nusers, nitems, seed))
+
+
+def zipf_permutation(nitems, seed):
+    """(pa, pb) of the rank → item bijection (pa·r + pb) mod nitems, as launch_synth_keys_zipf
+    derives them: pa the first odd number from ⌊nitems·(golden ratio − 1)⌋ | 1 upwards that is
+    coprime to nitems (1 for nitems ≤ 1), reduced mod nitems; pb = mix64(seed ^ 0x7a1f) mod
+    nitems."""
+    pa = int(float(nitems) * 0.6180339887498949) | 1
+    if nitems <= 1:
+        pa = 1
+    while nitems > 1 and np.gcd(pa, nitems) != 1:
+        pa += 2
+    return pa % max(nitems, 1), mix64(seed ^ 0x7A1F) % max(nitems, 1)
+
+
+ZIPF_MARGIN = 1e-12
+
+
+def zipf_ambiguous(x):
+    """⌊x·(1 − 1e-12)⌋ ≠ ⌊x·(1 + 1e-12)⌋, elementwise: x is too near an integer for its floor
+    to be the same under every correctly working exp/log/pow."""
+    x = np.asarray(x, np.float64)
+    return ~(np.floor(x * (1.0 - ZIPF_MARGIN)) == np.floor(x * (1.0 + ZIPF_MARGIN)))
+
+
+def zipf_draws(nusers, nitems, ndraws, seed, s):
+    """(user, rank, ambiguous) of each draw of synth_keys_zipf_kernel: h1 = mix64(seed ^
+    mix64(i)), h2 = mix64(h1 ^ 0x2545f4914f6cdd1d), user = (h1·nusers) >> 64, u01 = (h2 >> 11)·
+    2⁻⁵³, x = exp(u01·ln(nitems + 1)) for |s − 1| < 1e-12 and ((nitems + 1)ᵉ − 1)·u01 + 1 to the
+    power 1/e, e = 1 − s, otherwise; rank = ⌊x⌋ − 1 for x ≥ 1, else 0, clamped to nitems − 1.
+    A draw is ambiguous when ⌊x·(1 − 1e-12)⌋ ≠ ⌊x·(1 + 1e-12)⌋ (the device's exp/log/pow may
+    differ from numpy's in the last bits: x = exp(t), t < 45, a few ulp of t are 2e-14 of x)
+    or, for s ≠ 1, when moving the power's base by ± 2⁻⁵² (one rounding of the `·u01 + 1`,
+    which the device may fuse) moves ⌊x⌋."""
+    h1 = mix64_np(_U(seed) ^ mix64_np(np.arange(ndraws, dtype=_U)))
+    h2 = mix64_np(h1 ^ _U(0x2545F4914F6CDD1D))
+    users = mulhi64_np(h1, nusers)
+    u01 = (h2 >> _U(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+    top = float(nitems) + 1.0
+    if abs(s - 1.0) < 1e-12:
+        x = np.exp(u01 * np.log(top))
+        near = [x]
+    else:
+        e = 1.0 - s
+        base = (np.power(top, e) - 1.0) * u01 + 1.0
+        x = np.power(base, 1.0 / e)
+        near = [np.power(base - 2.0 ** -52, 1.0 / e), np.power(base + 2.0 ** -52, 1.0 / e)]
+    ambiguous = zipf_ambiguous(x)
+    for y in near:
+        ambiguous |= ~(np.floor(y) == np.floor(x))  # a NaN counts as ambiguous
+    rank = np.where(x >= 1.0, np.floor(x) - 1.0, 0.0).astype(_U)
+    return users, np.minimum(rank, _U(nitems - 1)), ambiguous
+
+
+@functools.lru_cache(maxsize=None)
+def zipf_reference(nusers, nitems, ndraws, seed, s):
+    """What qmfx_gen_synthetic_zipf(nusers, nitems, ndraws, seed, s) leaves in a context, s > 0:
+    (m, (urp, ucol, uval), (irp, icol, ival), number of ambiguous draws); the draws of
+    zipf_draws, item = (pa·rank + pb) mod nitems (zipf_permutation), key = user·nitems + item,
+    then as synth_reference.  Exact only when no draw is ambiguous.  Cached: read-only."""
+    users, rank, ambiguous = zipf_draws(nusers, nitems, ndraws, seed, s)
+    pa, pb = zipf_permutation(nitems, seed)
+    items = (_U(pa) * rank + _U(pb)) % _U(nitems)  # pa, rank < 2³¹: no wrap
+    keys = np.unique(users * _U(nitems) + items)
+    return (len(keys), *_csr_pair(keys, nusers, nitems, seed), int(np.count_nonzero(ambiguous)))
+
+
+def fill_reference(n, k, bound, seed, precision):
+    """The n×k matrix qmfx_fill_uniform(side, bound, seed) writes: entry (r, c) is
+    (2·u01 − 1)·bound in double, u01 = (mix64(seed ^ mix64(r·k + c)) >> 11)·2⁻⁵³, rounded to
+    fp32 (then widened) for precision 32."""
+    h = mix64_np(_U(seed) ^ mix64_np(np.arange(n * k, dtype=_U)))
+    u01 = (h >> _U(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+    out = ((2.0 * u01 - 1.0) * bound).reshape(n, k)
+    if precision == 32:
+        out = out.astype(np.float32).astype(np.float64)
+    return out
+
+
+# the cases of tests/test_synth_gpu.py: (nusers, nitems, nnz, seed), keyed by test id.  The CPU
+# module checks the properties each is there for.
+SEED_MAX = M64
+SEED_WRAP = 0x9E3779B97F4A7C15  # seed·31 + 7 ≥ 2⁶⁴
+ROW_EDGES = (1, 2, 255, 256, 257, 511, 512)  # rowptr_from_keys_kernel: n + 1 entries, 256 a block
+SYNTH_CASES = {}
+for _n in ROW_EDGES:
+    SYNTH_CASES["users%d" % _n] = (_n, 37, max(1, _n * 37 // 4), 11)
+    SYNTH_CASES["items%d" % _n] = (37, _n, max(1, _n * 37 // 4), 12)
+SYNTH_CASES.update({
+    "empty_rows": (5000, 7, 40, 13),
+    "one_item": (300, 1, 150, 14),
+    "one_user": (1, 300, 150, 15),
+    # the radix sort's end_bit: space 2¹³, 2¹² − 1, 2¹² + 1 and 1.4995·2¹² (83·74: a third of the
+    # keys have bit 12 set); 63·65, 17·241 and 83·74 are coprime pairs
+    "space_pow2": (64, 128, 2730, 16),
+    "space_pow2_minus1": (63, 65, 1365, 17),
+    "space_pow2_plus1": (17, 241, 1365, 18),
+    "space_1p5_pow2": (83, 74, 2047, 19),
+    # key space 5.2e9 > 2³²: the product's high word, the sort, 64-bit / and %
+    "space_gt32_users": ((1 << 20) + 3, 5003, 20000, 20),
+    "space_gt32_items": (5003, (1 << 20) + 3, 20000, 21),
+    # nnz = space / 2, the most the call takes: many repeated draws
+    "collisions": (31, 33, 31 * 33 // 2, 22),
+    "seed0": (257, 129, 5000, 0),
+    "seed_max": (257, 129, 5000, SEED_MAX),
+    "seed_wrap": (257, 129, 5000, SEED_WRAP),
+})
+# (nusers, nitems, ndraws, seed, s); at nitems ≤ 2 the draws outnumber the pairs there are
+ZIPF_S = (0.5, 1.0, 2.0, 8.0)
+ZIPF_CASES = {}
+for _j, (_nu, _ni, _nd) in enumerate(((300, 1, 2000), (300, 2, 2000), (777, 1000, 50000),
+                                      (1237, 5003, 100000))):
+    for _s in ZIPF_S:
+        ZIPF_CASES["items%d-s%g" % (_ni, _s)] = (_nu, _ni, _nd, 100 + 10 * _j + int(_s), _s)
