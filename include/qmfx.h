@@ -222,6 +222,57 @@ int qmfx_recommend_candidates(qmfx_ctx* ctx, int64_t nusers, const int64_t* user
                               int64_t* items /*nusers·topn*/, double* scores /*nusers·topn*/,
                               int32_t* counts /*nusers*/);
 
+/* ---- screened recommendations: an f32 filter, an exact re-rank, identical lists ----------------
+ * qmfx_recommend_screened returns items, scores and counts of qmfx_recommend for the same
+ * arguments, bit for bit (tie rule, -1 / 0.0 tail, the three exclude modes, the own-rows rule of
+ * QMFX_REC_UNSEEN_SIGNALS on a sharded context, use_biases), for every input qmfx_recommend
+ * accepts; `sample` and `cap` only move work between the stages and never change the answer.
+ * It scores the whole catalogue once in f32 on the matrix cores and scores exactly only what the
+ * f32 pass cannot rule out:
+ *   Sample      the S = `sample` items floor(j * nitems / S), j = 0..S-1.
+ *   Threshold   L_u = the score at rank topn-1 of user u's exact top-N within the sample (same
+ *               exclude and bias; the shared-list form of qmfx_recommend_candidates).  A user
+ *               whose sample holds fewer than topn eligible items is answered by the exact scan
+ *               (qmfx_recommend's).
+ *   Screen      a(u, i) = the f32 fma chain s = fmaf(u^_f, q^_f, s), f = 0..k-1 from s = 0, of the
+ *               rows rounded to f32 (round to nearest even; the identity on an fp32 context).
+ *   Slack       eps(u, i) = (k + 4) * 2^-23 * nu * nq  +  (k + 4) * 2^-52 * |b_i|
+ *                           +  2^-116 * (1 + nu + nq),
+ *               nu and nq the values qmfx_factor_norms returns for the user's and the item's row,
+ *               b_i the item's bias (0 without use_biases), evaluated in double.
+ *   Pass rule   item i passes for user u unless a is finite and (double)a + b_i < L_u - eps(u, i),
+ *               each side one rounded double operation.  A non-finite a always passes.  Seen
+ *               items are not looked at here.
+ *   Re-rank     a user with at most `cap` passing items is ranked exactly within them (the
+ *               per-user form of qmfx_recommend_candidates, lists ascending); a user with more
+ *               is answered by the exact scan.
+ * Why the lists are identical: every item of the true top-N has an exact score >= the true N-th
+ * score >= L_u (the sample is part of the catalogue), |a + b_i - score| <= eps(u, i) whenever a is
+ * finite (DESIGN 3.12 derives the constants: one f32 rounding per operand, the f32 chain's
+ * gamma_k, Cauchy-Schwarz, the double score's own roundings, and the absolute term for f32
+ * underflow with or without subnormals), and rounding is monotone; so it passes, and ranking
+ * exactly within a superset of the top-N gives the top-N.
+ * sample = 0 / cap = 0 choose them: S = sqrt(8 * topn * nitems) up to a multiple of 64, cap =
+ * 4 * topn * nitems / S + 64.  With both 0 a catalogue too small for the screen to pay off is
+ * answered by qmfx_recommend's path alone; an explicit sample or cap always screens.
+ * Fails (-1, with a message, before anything is launched) on everything qmfx_recommend rejects,
+ * on sample not 0 and outside topn..nitems, and on cap not 0 and below topn.  nusers == 0
+ * succeeds and touches nothing.  The call leaves the factors, CSR, biases and every cached state
+ * untouched; f32 copies and norms are made per call; scratch is sized from the request and owned
+ * by the context.  Its device time is counted in qmfx_solve_kernel_stats with 2k flop per (user,
+ * item scanned) pair, as qmfx_recommend's is.
+ * qmfx_recommend_screen_stats, of the last screened call: [0] users answered through the screen,
+ * [1] users answered by the exact scan, [2] candidates kept in total, [3] the longest kept list.
+ * qmfx_recommend_screen_stage_ms, of the last screened call: milliseconds on the device stream of
+ * [0] sample, [1] rows / norms / f32 copies, [2] screen, [3] counters to the host and sort,
+ * [4] re-rank, [5] exact scan (all 0 when the call took the dense path). */
+int qmfx_recommend_screened(qmfx_ctx* ctx, int64_t nusers, const int64_t* users, int topn,
+                            int exclude, int use_biases, int64_t sample /*0 = auto*/,
+                            int64_t cap /*0 = auto*/, int64_t* items /*nusers·topn*/,
+                            double* scores /*nusers·topn*/, int32_t* counts /*nusers*/);
+int qmfx_recommend_screen_stats(qmfx_ctx* ctx, int64_t out[4]);
+int qmfx_recommend_screen_stage_ms(qmfx_ctx* ctx, double out[6]);
+
 /* ---- similar rows: top-N neighbours in factor space ----------------------------------------
  * For each of the nq query rows of `side` (row idx; any order, repeats allowed) the device
  * scores every row of the same side against the query row and selects the best eligible ones,

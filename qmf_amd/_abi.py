@@ -61,6 +61,10 @@ SIGNATURES = {
                                P_i32],
     "qmfx_recommend_candidates": [vp, c_i64, P_i64, P_i64, c_i64, P_i64, c_int, c_int, c_int,
                                   P_i64, P_f64, P_i32],
+    "qmfx_recommend_screened": [vp, c_i64, P_i64, c_int, c_int, c_int, c_i64, c_i64, P_i64,
+                                P_f64, P_i32],
+    "qmfx_recommend_screen_stats": [vp, P_i64],
+    "qmfx_recommend_screen_stage_ms": [vp, P_f64],
     "qmfx_factor_norms": [vp, c_int, P_f64],
     "qmfx_similar": [vp, c_int, c_i64, P_i64, c_int, c_int, c_int, P_i64, P_f64, P_i32],
     "qmfx_wals_fold_in": [vp, c_int, c_i64, P_i64, P_i32, P_f64, c_dbl, c_dbl, P_f64, P_f64, P_i64],
@@ -406,6 +410,31 @@ class Context:
                                     int(use_biases), _p(items, P_i64), _p(scores, P_f64),
                                     _p(counts, P_i32)))
         return items, scores, counts
+
+    def recommend_screened(self, users, topn, exclude=0, use_biases=False, sample=0, cap=0):
+        """recommend(), bit for bit, through an f32 screen of the catalogue and an exact re-rank
+        of what it keeps: see include/qmfx.h qmfx_recommend_screened (sample, cap: 0 = auto)."""
+        users = np.ascontiguousarray(users, np.int64)
+        items, scores, counts = self._topn_out(len(users), topn)
+        _check(lib().qmfx_recommend_screened(self.h, len(users), _p(users, P_i64), int(topn),
+                                             int(exclude), int(use_biases), int(sample), int(cap),
+                                             _p(items, P_i64), _p(scores, P_f64),
+                                             _p(counts, P_i32)))
+        return items, scores, counts
+
+    def screen_stats(self):
+        """Of the last recommend_screened: [users through the screen, users through the exact
+        scan, candidates kept, longest kept list]."""
+        out = np.zeros(4, np.int64)
+        _check(lib().qmfx_recommend_screen_stats(self.h, _p(out, P_i64)))
+        return out
+
+    def screen_stage_ms(self):
+        """Of the last recommend_screened: device milliseconds of [sample, rows / norms / f32
+        copies, screen, counters + sort, re-rank, exact scan]."""
+        out = np.zeros(6, np.float64)
+        _check(lib().qmfx_recommend_screen_stage_ms(self.h, _p(out, P_f64)))
+        return out
 
     def _topn_out(self, n, topn):
         w = max(int(topn), 0)

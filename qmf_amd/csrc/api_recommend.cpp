@@ -5,7 +5,7 @@
 
 using namespace qmfx;
 
-namespace {
+namespace qmfx {
 
 // What every recommend call rejects before it touches the device.
 int rec_check(const qmfx_ctx* c, int64_t nusers, const int64_t* users, int topn, int exclude,
@@ -34,21 +34,9 @@ int rec_check(const qmfx_ctx* c, int64_t nusers, const int64_t* users, int topn,
   return 0;
 }
 
-// The factors, biases and seen lists of a recommend call.
-template <typename T>
-void rec_model(const qmfx_ctx* c, RecArgs<T>& a, int exclude, int use_biases) {
-  const SideBuf& su = c->s[0];
-  a.U = c->s[0].F.as<T>();
-  a.I = c->s[1].F.as<T>();
-  a.bias = use_biases ? c->bias.as<T>() : nullptr;
-  if (exclude == QMFX_REC_UNSEEN_SIGNALS) {
-    a.seen_ptr = su.rowptr;
-    a.seen_col = colp(su);
-  } else if (exclude == QMFX_REC_UNSEEN_POSITIVES) {
-    a.seen_ptr = c->urowptr;
-    a.seen_col = c->uitems;
-  }
-}
+}  // namespace qmfx
+
+namespace {
 
 // The call's kernels (between ev0 and ev1), for qmfx_solve_kernel_stats.
 int rec_account(qmfx_ctx* c, double flops, double bytes) {
@@ -58,10 +46,12 @@ int rec_account(qmfx_ctx* c, double flops, double bytes) {
   return 0;
 }
 
+}  // namespace
+
 // qmfx_recommend, with the ndeny items of `deny` eligible for nobody.
-int recommend_dense(qmfx_ctx* c, int64_t nusers, const int64_t* users, int64_t ndeny,
-                    const int64_t* deny, int topn, int exclude, int use_biases, int64_t* items,
-                    double* scores, int32_t* counts) {
+int qmfx::recommend_dense(qmfx_ctx* c, int64_t nusers, const int64_t* users, int64_t ndeny,
+                          const int64_t* deny, int topn, int exclude, int use_biases,
+                          int64_t* items, double* scores, int32_t* counts) {
   if (nusers == 0) return 0;
   if (ndeny < 0) return fail("ndeny out of range");
   if (int rc = rec_check(c, nusers, users, topn, exclude, use_biases)) return rc;
@@ -98,6 +88,8 @@ int recommend_dense(qmfx_ctx* c, int64_t nusers, const int64_t* users, int64_t n
   if (int r = topn_copy_out(c, nusers, topn, items, scores, counts)) return r;
   return rec_account(c, topn_flops(c, nusers, ni), topn_bytes(c, nusers, ni));
 }
+
+namespace {
 
 // cand[b .. e) as int32 into out: strictly ascending item rows
 int take_list(const int64_t* cand, int64_t b, int64_t e, int64_t ni, int32_t* out) {

@@ -122,6 +122,23 @@ struct TopN {
   Scratch<int64_t> cptr, woff;
 };
 
+// Scratch of the screened top-N (qmfx_recommend_screened): the requested rows gathered, the f32
+// copies of an fp64 context's rows, both sides' norms, the thresholds, pass counters and kept
+// lists, the sort keys, and the exact-scan users with their outputs.
+struct Screen {
+  Scratch<void> ug;                  // [nreq][kp] context precision
+  Scratch<float> uf, itf;            // fp64 contexts: [nreq][kp], [nitems][kp]
+  Scratch<double> unorm, inorm, thr;
+  Scratch<int32_t> cnt, scnt, list;
+  Scratch<uint64_t> keys, keys2;
+  Scratch<int64_t> xusers, xitems;
+  Scratch<double> xscores;
+  Scratch<int32_t> xcounts;
+  Event ev[7];                       // stage boundaries (created by the first call)
+  int64_t stats[4] = {0, 0, 0, 0};   // qmfx_recommend_screen_stats
+  double stage_ms[6] = {0, 0, 0, 0, 0, 0};  // qmfx_recommend_screen_stage_ms
+};
+
 }  // namespace qmfx
 
 // Members are destroyed last to first: the streams stand first, so they outlive every buffer
@@ -177,6 +194,7 @@ struct qmfx_ctx {
   // The serving calls' scratch: every buffer knows the bytes it holds and is grown on demand
   // (reserve).  Top-N selection (qmfx_recommend, qmfx_similar, qmfx_recommend_fold_in):
   qmfx::TopN rc;
+  qmfx::Screen scr;
   // rows given with a call as a CSR of their own (fold-in, qmfx_wals_explain_rows): the last
   // upload (upload_rows, rows.h)
   qmfx::Scratch<int64_t> fr_rowptr;
@@ -369,11 +387,35 @@ inline double topn_bytes(const qmfx_ctx* c, int64_t nreq, int64_t ncand) {
   return (double)((nreq + 31) / 32) * (double)ncand * c->k * (double)c->esz;
 }
 
+// api_recommend.cpp, shared with api_screened.cpp: what every recommend call rejects before it
+// touches the device, and qmfx_recommend with the ndeny items of `deny` eligible for nobody
+int rec_check(const qmfx_ctx* c, int64_t nusers, const int64_t* users, int topn, int exclude,
+              int use_biases);
+int recommend_dense(qmfx_ctx* c, int64_t nusers, const int64_t* users, int64_t ndeny,
+                    const int64_t* deny, int topn, int exclude, int use_biases, int64_t* items,
+                    double* scores, int32_t* counts);
+
 // col/val as the kernels index them: with the global rowptr (see SideBuf::shard_off)
 inline int32_t* colp(const SideBuf& sb) { return sb.col - sb.shard_off; }
 template <typename T>
 const T* valp(const SideBuf& sb) {
   return sb.val.as<T>() - sb.shard_off;
+}
+
+// The factors, biases and seen lists of a recommend call.
+template <typename T>
+void rec_model(const qmfx_ctx* c, RecArgs<T>& a, int exclude, int use_biases) {
+  const SideBuf& su = c->s[0];
+  a.U = c->s[0].F.as<T>();
+  a.I = c->s[1].F.as<T>();
+  a.bias = use_biases ? c->bias.as<T>() : nullptr;
+  if (exclude == QMFX_REC_UNSEEN_SIGNALS) {
+    a.seen_ptr = su.rowptr;
+    a.seen_col = colp(su);
+  } else if (exclude == QMFX_REC_UNSEEN_POSITIVES) {
+    a.seen_ptr = c->urowptr;
+    a.seen_col = c->uitems;
+  }
 }
 
 inline int ensure_side_factors(qmfx_ctx* c, int side) {

@@ -348,6 +348,45 @@ hipError_t launch_factor_norms(const float* F, int64_t n, int k, int kp, double*
 hipError_t launch_factor_norms(const double* F, int64_t n, int k, int kp, double* norms,
                                hipStream_t s);
 
+// The screen of qmfx_recommend_screened (screen.hip): an f32 MFMA scan of request × catalogue
+// that appends to user t's list every item the bound of include/qmfx.h cannot rule out of the
+// user's top-N.  T is the context precision (the type of the biases).
+constexpr int kScreenTileUsers = 128, kScreenTileItems = 128;  // a workgroup's tile
+template <typename T>
+struct ScreenArgs {
+  const float* A;            // [nreq][kp] the requested users' rows, rounded to f32
+  const float* B;            // [nitems][kp] the items' rows, rounded to f32
+  const T* bias;             // [nitems] item biases or nullptr
+  int64_t nreq, nitems;
+  int k, kp;
+  const double* unorm;       // [nreq] norms of the requested rows (launch_factor_norms)
+  const double* inorm;       // [nitems]
+  const double* thr;         // [nreq] L_u; +inf: nothing finite passes
+  int32_t* cnt;              // [nreq] passing items, zero on entry; runs past cap
+  int32_t* list;             // [nreq][cap] the first cap passing items, in no order
+  int64_t cap;
+  int64_t itiles;            // set by the launcher: item tiles
+};
+// workgroups of a scan (one grid dimension); a launch's thread count must fit 32 bits, so a scan
+// of more than kScreenMaxTiles is refused
+constexpr int64_t kScreenMaxTiles = ((int64_t)1 << 31) / 256 - 1;
+int64_t screen_tiles(int64_t nreq, int64_t nitems);
+hipError_t launch_screen(const ScreenArgs<float>& a, hipStream_t s);
+hipError_t launch_screen(const ScreenArgs<double>& a, hipStream_t s);
+// out[t][·] = U[users[t]][·] (all kp columns)
+hipError_t launch_screen_gather(const float* U, const int64_t* users, int64_t nreq, int kp,
+                                float* out, hipStream_t s);
+hipError_t launch_screen_gather(const double* U, const int64_t* users, int64_t nreq, int kp,
+                                double* out, hipStream_t s);
+hipError_t launch_screen_f32(const double* in, int64_t n, float* out, hipStream_t s);
+// thr[t] = scores[t][topn − 1] when counts[t] == topn, else +inf; cnt[t] = 0; scnt[t] = counts[t]
+hipError_t launch_screen_prep(const double* scores, const int32_t* counts, int64_t nreq, int topn,
+                              double* thr, int32_t* cnt, int32_t* scnt, hipStream_t s);
+// keys[cptr[t] + j] = t << 32 | list[t][j], j < cptr[t + 1] − cptr[t]; and the items back out
+hipError_t launch_screen_keys(const int32_t* list, const int64_t* cptr, int64_t nreq, int64_t cap,
+                              uint64_t* keys, hipStream_t s);
+hipError_t launch_screen_unpack(const uint64_t* keys, int64_t n, int32_t* cand, hipStream_t s);
+
 // Fold-in (foldin.hip): the row plan of a foreign CSR, built on the device.
 // A row's sort key, low bits first: [row : row_bits][field : n_bits][direct : 1].  Whitened
 // rows (bucket NTN = (max(n, 1) + 15) / 16 ≤ max_ntn) carry field = NTN − 1, direct rows

@@ -305,6 +305,8 @@ void Engine::saveRecommendations(qmfx_ctx* ctx, const int exclude, const bool us
   CHECK((scope.excludeItemIds != nullptr) + (scope.itemIds != nullptr) +
             (scope.candidates != nullptr) <= 1)
       << "a recommendation scope sets at most one of its lists";
+  CHECK(!scope.screen || (!scope.excludeItemIds && !scope.itemIds && !scope.candidates))
+      << "the screened route scans the whole catalogue: it takes no item or candidate list";
   const int n = static_cast<int>(topN), biases = useBiases ? 1 : 0;
   if (scope.candidates) {
     CHECK(!userIds) << "per-user candidates name their own users";
@@ -369,9 +371,14 @@ void Engine::saveRecommendations(qmfx_ctx* ctx, const int exclude, const bool us
   savePairs(userIndex, itemIndex, users, fileName, topN,
             [&](const int64_t* rows, const size_t n, int64_t* items, double* scores,
                 int32_t* counts) {
-              QMFX_CHECK(qmfx_recommend(ctx, static_cast<int64_t>(n), rows,
-                                        static_cast<int>(topN), exclude, useBiases ? 1 : 0,
-                                        items, scores, counts));
+              if (scope.screen)
+                QMFX_CHECK(qmfx_recommend_screened(ctx, static_cast<int64_t>(n), rows,
+                                                   static_cast<int>(topN), exclude,
+                                                   useBiases ? 1 : 0, 0, 0, items, scores, counts));
+              else
+                QMFX_CHECK(qmfx_recommend(ctx, static_cast<int64_t>(n), rows,
+                                          static_cast<int>(topN), exclude, useBiases ? 1 : 0,
+                                          items, scores, counts));
             },
             after);
 }

@@ -28,6 +28,10 @@ struct RecommendScope {
   // items listed with them, and the requested users are exactly the lines' known users, in
   // ascending user idx; excludes userIds
   const std::vector<DatasetElem>* candidates = nullptr;
+  // not a narrower scope but another route to the same lists: the whole catalogue through
+  // qmfx_recommend_screened (an f32 screen, then an exact re-rank; the file is byte for byte
+  // the one written without it).  Only without a list above.
+  bool screen = false;
 };
 
 class Engine {

@@ -55,6 +55,9 @@ DEFINE_string(item_factors, "", "filename of item factors");
 DEFINE_string(user_recommendations, "", "filename of the users' top-N recommendations");
 DEFINE_uint64(num_recommendations, 10, "items recommended per user (1..128)");
 DEFINE_bool(recommend_seen, false, "also recommend items of the user's training data");
+DEFINE_bool(recommend_screen, false,
+            "select --user_recommendations through the f32 screen and exact re-rank "
+            "(qmfx_recommend_screened): the same file, faster on large catalogues");
 DEFINE_string(recommend_users, "",
               "file with one user id per line to recommend for (default: every training user)");
 DEFINE_string(recommend_exclude_items, "",
@@ -103,6 +106,9 @@ int main(int argc, char** argv) {
     // what may be recommended: at most one of the three scope flags, on --user_recommendations
     const int scopes = !FLAGS_recommend_exclude_items.empty() + !FLAGS_recommend_items.empty() +
                        !FLAGS_recommend_candidates.empty();
+    CHECK(!FLAGS_recommend_screen || scopes == 0)
+        << "--recommend_screen scans the whole catalogue: it does not combine with "
+           "--recommend_exclude_items, --recommend_items or --recommend_candidates";
     CHECK(scopes <= 1) << "--recommend_exclude_items, --recommend_items and "
                           "--recommend_candidates are mutually exclusive";
     CHECK(FLAGS_recommend_candidates.empty() || FLAGS_recommend_users.empty())
@@ -147,6 +153,7 @@ int main(int argc, char** argv) {
     std::vector<int64_t> scopeIds;
     std::vector<qmf::DatasetElem> scopeLines;
     qmf::RecommendScope scope;
+    scope.screen = FLAGS_recommend_screen;
     if (!FLAGS_recommend_exclude_items.empty()) {
       scopeIds = qmf::readIds(FLAGS_recommend_exclude_items);
       scope.excludeItemIds = &scopeIds;
