@@ -352,6 +352,64 @@ int qmfx_recommend_fold_in(qmfx_ctx* ctx, int64_t nrows, const int64_t* rowptr,
                            double* scores /*nrows·topn*/, int32_t* counts /*nrows*/,
                            double* factors /*NULL or nrows·k*/);
 
+/* ---- BPR fold-in: new users' rows by SGD, items frozen ------------------------------------------
+ * qmfx_bpr_fold_in fits nrows new user rows against the context's current item factors (and item
+ * biases with use_biases), which are read and never written: BPREngine::update's user line alone.
+ * The rows come as a CSR of their own: rowptr[nrows+1], colidx = the row's positive items (item
+ * idx), strictly ascending within a row: c_0 < c_1 < ... < c_{n-1}.  Every row is deterministic:
+ * its result depends on its own positives, their position in the call's CSR, the seed, the
+ * schedule and the items, not on the launch.
+ *   Start     p = init[r*k + f] rounded to the context precision; 0.0 with init == NULL.
+ *   Passes    for pass e = 0..nepochs-1, for i = 0..n-1 in CSR order in every pass, for
+ *             j = 0..num_neg-1: one step on (p, q_{c_i}, q_{n_ij}) at the rate lr_e, with
+ *             lr_0 = lr, lr_{e+1} = lr_e * decay in double (BPREngine::optimize's rule), each
+ *             rounded once to the context precision.
+ *   Draw      qmfx_bpr_epoch's counter-based sampler, in integer arithmetic:
+ *             seed_key = mix64(seed ^ 0xb5ad4eceda1ce2a9),
+ *             pkey = mix64(mix64(seed_key ^ e) ^ (rowptr[r] + i)), fk = lo32(pkey) ^ hi32(pkey);
+ *             attempt t of draw j is cand = (fmix32(fk + (4099*j + t) * 0x9e3779b9) * nitems) >> 32
+ *             (mix64: the splitmix64 finaliser, fmix32: murmur3's).  A draw is accepted when cand
+ *             is not among the row's positives, or when t >= 4096: a capped draw is used as drawn,
+ *             even when it equals c_i.
+ *   Step      x = sum_f p_f * (qp_f - qn_f), plus b_p - b_n with use_biases; eg = 1 / (1 + e^x);
+ *             p_f <- p_f + lr_e * (eg * (qp_f - qn_f) - user_lambda * p_f), in the context
+ *             precision.  A non-finite eg skips the step and flags the call.
+ *   Loss      losses[r] = the sum over the steps of the LAST pass, in step order, of
+ *             log(1 + exp(-(double)x)), x the step's value before its update.
+ * A row without positives keeps its start value and has loss 0.0.  factors[r*k + f] carries the
+ * values the device holds, widened, as qmfx_wals_fold_in's does.
+ * qmfx_bpr_recommend_fold_in folds the rows in, then selects each new row's top-N exactly as
+ * qmfx_recommend defines it: the scores are qmfx_recommend's, bit for bit, on the device-held
+ * folded rows and item factors, with the item bias when use_biases; the same order and tie rule;
+ * the unused tail is -1 / 0.0.  exclude_seen != 0 removes the row's own colidx.  topn is
+ * 1..QMFX_REC_MAX_N.  factors (NULL or nrows*k) receives the folded rows, bit for bit those of
+ * qmfx_bpr_fold_in.
+ * The context needs only the shape and the item factors (qmfx_set_shape + qmfx_set_factors), plus
+ * the biases when use_biases: no user factors, no positives, no CSR.  The calls leave the factors,
+ * biases, positives, cached evaluation triplets and everything the last half or epoch reported
+ * untouched; the rows, their losses and the passes' rates live in scratch sized from the request
+ * and owned by the context (shared with the other fold-in calls).  Both work on any rank of a
+ * sharded context, the factors being full replicas.
+ * Fail (-1, with a message, before anything is launched) on: no item factors, use_biases without
+ * biases, rowptr[0] != 0 or rowptr decreasing, a column index out of range, a row that is not
+ * strictly ascending, nepochs < 1 or num_neg < 1, topn out of range, nfactors > 256, nrows or
+ * rowptr[nrows] >= 2^31.  nrows == 0 succeeds and touches nothing.  When a step was flagged the
+ * call returns -4 with qmfx_bpr_epoch's message, after the outputs are filled.
+ * Their device time is counted in qmfx_solve_kernel_stats with the work steps * 6k flop and
+ * steps * 2 * kp * (element size) bytes, steps = nepochs * num_neg * rowptr[nrows] and kp = k
+ * rounded up to a multiple of 16; the recommend form adds qmfx_recommend's terms. */
+int qmfx_bpr_fold_in(qmfx_ctx* ctx, int64_t nrows, const int64_t* rowptr /*nrows+1*/,
+                     const int32_t* colidx /*item idx, strictly ascending per row*/,
+                     const double* init /*NULL or nrows·k*/, uint64_t seed, int nepochs,
+                     int num_neg, double lr, double decay, double user_lambda, int use_biases,
+                     double* factors /*nrows·k*/, double* losses /*NULL or nrows*/);
+int qmfx_bpr_recommend_fold_in(qmfx_ctx* ctx, int64_t nrows, const int64_t* rowptr,
+                               const int32_t* colidx, const double* init, uint64_t seed,
+                               int nepochs, int num_neg, double lr, double decay,
+                               double user_lambda, int use_biases, int topn, int exclude_seen,
+                               int64_t* items /*nrows·topn*/, double* scores /*nrows·topn*/,
+                               int32_t* counts /*nrows*/, double* factors /*NULL or nrows·k*/);
+
 /* ---- explanations: per-signal contributions to a recommendation ------------------------------
  * WALS is the model of Hu, Koren and Volinsky (2008); with A = G + Σ αv·yyᵀ + λI and
  * x = A⁻¹ Σ (1+αv)·y the score of a target t splits over the row's own signals:
@@ -445,7 +503,8 @@ int qmfx_dist_plan(const int64_t* rowptr, int64_t nrows, int world, int npieces,
  * kernels of qmfx_bpr_epoch, qmfx_recommend and qmfx_similar calls are counted here too (one
  * unit of a similar call is 2k flop per (query, row) pair), and those of the fold-in calls
  * (planning and gather included; the work counted is the k×k form of every row), and those of
- * the explanation calls (the work formula stands with qmfx_wals_explain). */
+ * the explanation calls (the work formula stands with qmfx_wals_explain), and those of the BPR
+ * fold-in calls (the work formula stands with qmfx_bpr_fold_in). */
 int qmfx_solve_kernel_stats(qmfx_ctx* ctx, double* total_ms, int64_t* launches,
                             double* flops, double* bytes);
 /* Per kernel class since reset: 0 = direct row kernel, 1 = whitened row kernels (row solve

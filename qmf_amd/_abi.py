@@ -72,6 +72,10 @@ SIGNATURES = {
     "qmfx_fold_in_order": [vp, P_i64],
     "qmfx_recommend_fold_in": [vp, c_i64, P_i64, P_i32, P_f64, c_dbl, c_dbl, c_int, c_int, P_i64,
                                P_f64, P_i32, P_f64],
+    "qmfx_bpr_fold_in": [vp, c_i64, P_i64, P_i32, P_f64, c_u64, c_int, c_int, c_dbl, c_dbl, c_dbl,
+                         c_int, P_f64, P_f64],
+    "qmfx_bpr_recommend_fold_in": [vp, c_i64, P_i64, P_i32, P_f64, c_u64, c_int, c_int, c_dbl,
+                                   c_dbl, c_dbl, c_int, c_int, c_int, P_i64, P_f64, P_i32, P_f64],
     "qmfx_wals_explain": [vp, c_int, c_i64, P_i64, P_i64, P_i64, c_dbl, c_dbl, c_int, P_i64, P_i64,
                           P_f64, P_i32, P_f64, P_f64],
     "qmfx_wals_explain_rows": [vp, c_int, c_i64, P_i64, P_i32, P_f64, P_i64, P_i64, c_dbl, c_dbl,
@@ -542,6 +546,49 @@ class Context:
                                             _p(val, P_f64), float(alpha), float(lam), int(topn),
                                             int(bool(exclude_seen)), _p(items, P_i64),
                                             _p(scores, P_f64), _p(counts, P_i32), _p(F, P_f64)))
+        return items, scores, counts, F
+
+    # ---- BPR fold-in
+    def _bpr_rows(self, rowptr, colidx, init):
+        rp = np.ascontiguousarray(rowptr, np.int64)
+        col = np.ascontiguousarray(colidx, np.int32)
+        if len(rp) < 1:
+            raise QmfxError("fold-in CSR shape mismatch")
+        if init is not None:
+            init = np.ascontiguousarray(init, np.float64)
+            if init.shape != (len(rp) - 1, self.k):
+                raise QmfxError("init must be one row of nfactors per new row")
+        return rp, col, init
+
+    def bpr_fold_in(self, rowptr, colidx, seed, nepochs, num_neg, lr, decay, user_lambda,
+                    use_biases=False, init=None):
+        """(factors[n, k], losses[n]) of the n = len(rowptr) - 1 new users whose positive items
+        are the rows of the CSR (strictly ascending item indices), fitted by SGD against the
+        frozen item factors: see include/qmfx.h qmfx_bpr_fold_in."""
+        rp, col, init = self._bpr_rows(rowptr, colidx, init)
+        n = len(rp) - 1
+        F = np.empty((n, self.k), np.float64)
+        losses = np.empty(n, np.float64)
+        _check(lib().qmfx_bpr_fold_in(self.h, n, _p(rp, P_i64), _p(col, P_i32),
+                                      None if init is None else _p(init, P_f64), int(seed),
+                                      int(nepochs), int(num_neg), float(lr), float(decay),
+                                      float(user_lambda), int(bool(use_biases)), _p(F, P_f64),
+                                      _p(losses, P_f64)))
+        return F, losses
+
+    def bpr_recommend_fold_in(self, rowptr, colidx, seed, nepochs, num_neg, lr, decay,
+                              user_lambda, topn, use_biases=False, init=None, exclude_seen=True):
+        """(items[n, topn], scores[n, topn], counts[n], factors[n, k]) of n new users: see
+        include/qmfx.h qmfx_bpr_recommend_fold_in."""
+        rp, col, init = self._bpr_rows(rowptr, colidx, init)
+        n = len(rp) - 1
+        items, scores, counts = self._topn_out(n, topn)
+        F = np.empty((n, self.k), np.float64)
+        _check(lib().qmfx_bpr_recommend_fold_in(
+            self.h, n, _p(rp, P_i64), _p(col, P_i32), None if init is None else _p(init, P_f64),
+            int(seed), int(nepochs), int(num_neg), float(lr), float(decay), float(user_lambda),
+            int(bool(use_biases)), int(topn), int(bool(exclude_seen)), _p(items, P_i64),
+            _p(scores, P_f64), _p(counts, P_i32), _p(F, P_f64)))
         return items, scores, counts, F
 
     # ---- explanations

@@ -62,10 +62,10 @@ bool triplets_in_range(const qmfx_ctx* c, const int64_t* trip, int64_t n) {
   return true;
 }
 
-const char* const kBadGradients =
-    "gradients too big, try decreasing the learning rate (--init_learning_rate)";
-
 }  // namespace
+
+const char* const qmfx::kBadGradients =
+    "gradients too big, try decreasing the learning rate (--init_learning_rate)";
 
 // The positives index both sides' rows and urowptr is sized from the user count; the cached
 // triplets of qmfx_bpr_eval were range-checked against the shape they were uploaded under.

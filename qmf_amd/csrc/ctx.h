@@ -210,6 +210,9 @@ struct qmfx_ctx {
   qmfx::Scratch<qmfx::RowDesc> fi_desc;
   qmfx::Scratch<int64_t> fi_wb;
   qmfx::Scratch<double> fi_out;
+  // BPR fold-in (qmfx_bpr_fold_in, qmfx_bpr_recommend_fold_in) shares fr_rowptr / fr_col, fi_X,
+  // fi_rowloss and fi_out; its own: the passes' learning rates in the context precision
+  qmfx::Scratch<void> fi_lr;
   int64_t fi_classes[qmfx::kMaxNTN + 3] = {};
   int64_t fi_n = -1;  // rows of the last plan (-1: no fold-in yet)
   // explanations (qmfx_wals_explain, qmfx_wals_explain_rows): the uploaded queries, the
@@ -508,5 +511,6 @@ int shard_csr(qmfx_ctx* c, SideBuf& sb);
 void drop_eval_labels(qmfx_ctx* c);  // releases the test-label set (qmfx_eval_ranks then fails)
 // api_bpr.cpp
 void drop_bpr_positives(qmfx_ctx* c);  // releases the positives (qmfx_bpr_epoch then fails)
+extern const char* const kBadGradients;  // the message of a non-finite loss derivative (-4)
 
 }  // namespace qmfx

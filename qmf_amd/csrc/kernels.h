@@ -210,6 +210,32 @@ hipError_t launch_bpr_eval(const double* U, const double* I, const double* bias,
                            const int64_t* trip, int64_t n, int kp, int use_biases,
                            double* partial, double* out, hipStream_t s);
 
+// BPR fold-in (bpr_foldin.hip): SGD on new users' rows alone, items and biases frozen.  One
+// wave64 per row; row r starts from X[r] and ends there, its positives are col[rowptr[r]] ..
+// col[rowptr[r + 1]] (strictly ascending).
+template <typename T>
+struct BprFoldArgs {
+  const T* I;              // [ni][KP]
+  const T* bias;           // [ni], nullptr: no biases
+  const int64_t* rowptr;   // [nrows + 1]
+  const int32_t* col;
+  T* X;                    // [nrows][KP] in: start values, out: the folded rows
+  double* losses;          // [nrows] Σ log(1 + exp(−x̂)) over the last pass's steps
+  const T* lr;             // [nepochs] learning rate of every pass
+  int64_t nrows;
+  int64_t nitems;
+  int nepochs, num_neg;
+  uint64_t seed;
+  T user_lambda;
+  int kp;
+  int32_t* bad;            // set to 1 if a derivative was not finite
+  int grid;                // workgroups (waves); rows past it are reached by striding
+};
+// the launch's grid for nrows rows (QMFX_BPR_FOLD_GRID lowers it for the tests)
+int bpr_fold_grid(int64_t nrows);
+hipError_t launch_bpr_fold(const BprFoldArgs<float>& a, hipStream_t s);
+hipError_t launch_bpr_fold(const BprFoldArgs<double>& a, hipStream_t s);
+
 // Synthetic data + CSR build (data.hip)
 hipError_t launch_synth_keys(uint64_t* keys, int64_t n, uint64_t space, uint64_t seed,
                              hipStream_t s);

@@ -186,9 +186,10 @@ inline double direct_bytes(const qmfx_ctx* c, double nz, double nr) {
 
 // The one host pass over rows given as a CSR of their own: the CSR's shape and every column
 // index (an index out of range would be a device fault).  *max_n: the longest row.
+// need_values = false: the rows carry no values (qmfx_bpr_fold_in's positives).
 inline int validate_rows(int64_t nrows, const int64_t* rowptr, const int32_t* colidx,
                          const double* values, int64_t nother, bool need_ascending,
-                         int64_t* max_n) {
+                         int64_t* max_n, bool need_values = true) {
   if (nrows < 0 || nrows > 0x7fffffffll) return fail("nrows out of range (at most 2^31-1 rows)");
   if (!rowptr) return fail("rowptr is null");
   if (rowptr[0] != 0) return fail("rowptr[0] must be 0");
@@ -199,7 +200,7 @@ inline int validate_rows(int64_t nrows, const int64_t* rowptr, const int32_t* co
   }
   const int64_t nnz = rowptr[nrows];
   if (nnz > 0x7fffffffll) return fail("at most 2^31-1 signals in one fold-in call");
-  if (nnz > 0 && (!colidx || !values)) return fail("colidx or values is null");
+  if (nnz > 0 && (!colidx || (need_values && !values))) return fail("colidx or values is null");
   for (int64_t e = 0; e < nnz; ++e)
     if (colidx[e] < 0 || colidx[e] >= nother) return fail("column index out of range");
   if (need_ascending)
@@ -210,17 +211,19 @@ inline int validate_rows(int64_t nrows, const int64_t* rowptr, const int32_t* co
   *max_n = mx;
   return 0;
 }
-// validated rows → fr_rowptr / fr_col / fr_val (values in the context precision)
+// validated rows → fr_rowptr / fr_col / fr_val (values in the context precision; none when
+// `values` is null)
 inline int upload_rows(qmfx_ctx* c, int64_t nrows, const int64_t* rowptr, const int32_t* colidx,
                        const double* values) {
   const size_t n1 = (size_t)nrows, nnz = (size_t)rowptr[nrows], m1 = std::max<size_t>(nnz, 1);
   if (int rc = reserve(c->fr_rowptr, (n1 + 1) * 8)) return rc;
   if (int rc = reserve(c->fr_col, m1 * 4)) return rc;
-  if (int rc = reserve(c->fr_val, m1 * c->esz)) return rc;
+  if (values || nnz == 0)
+    if (int rc = reserve(c->fr_val, m1 * c->esz)) return rc;
   HIPCHK(scopy(c, c->fr_rowptr, rowptr, (n1 + 1) * 8, hipMemcpyHostToDevice));
   if (nnz > 0) {
     HIPCHK(scopy(c, c->fr_col, colidx, nnz * 4, hipMemcpyHostToDevice));
-    HIPCHK(copy_in(c, c->fr_val, values, nnz));
+    if (values) HIPCHK(copy_in(c, c->fr_val, values, nnz));
   }
   return 0;
 }

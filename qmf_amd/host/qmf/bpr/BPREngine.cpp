@@ -1,6 +1,7 @@
 #include <qmf/bpr/BPREngine.h>
 
 #include <algorithm>
+#include <fstream>
 
 #include <qmf/utils/Log.h>
 
@@ -244,6 +245,83 @@ void BPREngine::saveUserSimilarities(const std::string& fileName, const size_t t
                                   const bool cosine, const std::vector<int64_t>* userIds) const {
   CHECK(dev_) << "no factor data, have you initialized the engine?";
   saveSimilarities(dev_->get(), QMFX_USERS, userIndex_, fileName, topN, cosine, userIds);
+}
+
+size_t BPREngine::foldInUsers(const std::vector<DatasetElem>& lines,
+                              const std::string& userFactorsFile,
+                              const std::string& recommendationsFile, const size_t topN,
+                              const bool includeSeen, const size_t epochs) {
+  CHECK(dev_) << "no factor data, have you initialized the engine?";
+  CHECK_GE(epochs, 1u) << "fold-in needs at least one epoch";
+  if (!recommendationsFile.empty())
+    CHECK(topN >= 1 && topN <= QMFX_REC_MAX_N)
+        << "the number of recommendations must be in 1.." << QMFX_REC_MAX_N << ", got " << topN;
+  // (user id, item idx) of the positive lines whose item the model knows
+  std::vector<std::pair<int64_t, int32_t>> pairs;
+  pairs.reserve(lines.size());
+  size_t unknown = 0;
+  for (const auto& e : lines) {
+    if (e.value < 1.0) continue;
+    const size_t i = itemIndex_.idx(e.itemId);
+    if (i == IdIndex::missingIdx)
+      ++unknown;
+    else
+      pairs.emplace_back(e.userId, static_cast<int32_t>(i));
+  }
+  if (unknown > 0)
+    LOG(WARNING) << unknown << " fold-in lines name items that are not in the training data; dropped";
+  std::sort(pairs.begin(), pairs.end());
+  pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+  std::vector<int64_t> ids, rowptr(1, 0);
+  std::vector<int32_t> col(pairs.size());
+  for (size_t e = 0; e < pairs.size(); ++e) {
+    if (e == 0 || pairs[e].first != pairs[e - 1].first) {
+      if (e > 0) rowptr.push_back(static_cast<int64_t>(e));
+      ids.push_back(pairs[e].first);
+    }
+    col[e] = pairs[e].second;
+  }
+  if (!pairs.empty()) rowptr.push_back(static_cast<int64_t>(pairs.size()));
+  const size_t n = ids.size(), k = config_.nfactors;
+  if (n == 0) {
+    LOG(WARNING) << "no fold-in user has a positive on a known item; nothing folded in";
+    if (!userFactorsFile.empty()) std::ofstream(userFactorsFile).flush();
+    if (!recommendationsFile.empty()) std::ofstream(recommendationsFile).flush();
+    return 0;
+  }
+  IdIndex index;
+  index.assignSorted(std::move(ids));
+  FactorData folded(n, k);
+  qmfx_ctx* c = dev_->get();
+  const uint64_t seed = (static_cast<uint64_t>(gen_()) << 32) | gen_();
+  LOG(INFO) << "fold-in: " << n << " users, " << epochs << " epochs, sampling seed " << seed;
+  const int numNeg = static_cast<int>(config_.numNegativeSamples);
+  // optimize() decays the rate only below 1
+  const Double decay = config_.decayRate < 1.0 ? config_.decayRate : 1.0;
+  const int useBiases = config_.useBiases ? 1 : 0;
+  if (recommendationsFile.empty()) {
+    QMFX_CHECK(qmfx_bpr_fold_in(c, static_cast<int64_t>(n), rowptr.data(), col.data(), nullptr,
+                                seed, static_cast<int>(epochs), numNeg, config_.initLearningRate,
+                                decay, config_.userLambda, useBiases,
+                                folded.getFactors().data(), nullptr));
+  } else {
+    std::vector<int64_t> items(n * topN), rows(n);
+    std::vector<double> scores(n * topN);
+    std::vector<int32_t> counts(n);
+    for (size_t r = 0; r < n; ++r) rows[r] = static_cast<int64_t>(r);
+    QMFX_CHECK(qmfx_bpr_recommend_fold_in(
+        c, static_cast<int64_t>(n), rowptr.data(), col.data(), nullptr, seed,
+        static_cast<int>(epochs), numNeg, config_.initLearningRate, decay, config_.userLambda,
+        useBiases, static_cast<int>(topN), includeSeen ? 0 : 1, items.data(), scores.data(),
+        counts.data(), folded.getFactors().data()));
+    std::string text;
+    formatPairs(index, itemIndex_, rows.data(), 0, n, topN, items.data(), scores.data(),
+                counts.data(), text);
+    std::ofstream fout(recommendationsFile);
+    fout.write(text.data(), static_cast<std::streamsize>(text.size()));
+  }
+  if (!userFactorsFile.empty()) saveFactors(folded, index, userFactorsFile);
+  return n;
 }
 
 }  // namespace qmf

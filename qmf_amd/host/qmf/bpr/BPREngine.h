@@ -71,6 +71,21 @@ class BPREngine : public Engine {
                             const std::vector<int64_t>* userIds = nullptr) const override;
 
   // --- additions (not in the reference API) ---
+  // New users from "user item weight" lines (the training format): every user id of `lines`
+  // becomes one new row, fitted by SGD on that row alone against the trained item factors and
+  // biases, which stay as they are (qmfx_bpr_fold_in).  Lines with value < 1 are dropped as in
+  // init(); lines naming an item the model does not know are dropped with one warning; a
+  // user's items are sorted and deduplicated; a user id that was trained is folded in as a new
+  // row all the same.  `epochs` passes over a user's items with the config's
+  // numNegativeSamples, initLearningRate, decayRate, userLambda and useBiases; the sampling
+  // seed is drawn from the engine's generator (seed()).  Writes the users' factors
+  // (saveUserFactors' format, ascending id) and / or their top-N recommendations
+  // (saveUserRecommendations' format; includeSeen = false leaves out the user's own items);
+  // an empty file name skips that output.  Returns the number of users folded in.
+  size_t foldInUsers(const std::vector<DatasetElem>& lines, const std::string& userFactorsFile,
+                     const std::string& recommendationsFile, size_t topN, bool includeSeen,
+                     size_t epochs);
+
   struct PosNegTriplet {
     size_t userIdx;
     size_t posItemIdx;

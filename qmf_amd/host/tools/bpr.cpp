@@ -5,6 +5,12 @@
 // of --recommend_exclude_items, --recommend_items or --recommend_candidates (as in wals); and the
 // items' / users' nearest neighbours in factor space: --item_similarities,
 // --user_similarities, --num_similar, --similarity, --similar_item_ids, --similar_user_ids.
+// New users (as in wals): --fold_in_dataset FILE ("user item weight" lines, the training format;
+// its users are fitted by SGD against the trained item factors and biases, which stay as they
+// are; lines with weight < 1 and lines naming an unknown item are dropped, the latter with a
+// warning), --fold_in_user_factors OUT (the --user_factors format), --fold_in_recommendations
+// OUT (the --user_recommendations format, honouring --num_recommendations and
+// --recommend_seen) and --fold_in_epochs N (passes over a new user's items; default --nepochs).
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -77,6 +83,13 @@ DEFINE_string(similar_item_ids, "",
 DEFINE_string(similar_user_ids, "",
               "file with one user id per line to list neighbours for (default: every user)");
 
+// new users
+DEFINE_string(fold_in_dataset, "", "filename of new users' positives (the training format)");
+DEFINE_string(fold_in_user_factors, "", "filename of the folded-in users' factors");
+DEFINE_string(fold_in_recommendations, "",
+              "filename of the folded-in users' top-N recommendations");
+DEFINE_uint64(fold_in_epochs, 0, "SGD passes over a new user's items (0 = --nepochs)");
+
 int main(int argc, char** argv) {
   if (!qmf::flags::parse(&argc, &argv, "bpr")) return 1;
   if (FLAGS_user_factors.empty() || FLAGS_item_factors.empty()) {
@@ -99,7 +112,10 @@ int main(int argc, char** argv) {
   for (const auto& metric : qmf::split(FLAGS_test_avg_metrics, ',')) {
     CHECK(metricsEngine->addTestAvgMetric(metric)) << "metric " << metric << " is not available";
   }
-  if (!FLAGS_user_recommendations.empty())
+  if (!FLAGS_fold_in_user_factors.empty() || !FLAGS_fold_in_recommendations.empty())
+    CHECK(!FLAGS_fold_in_dataset.empty())
+        << "--fold_in_user_factors and --fold_in_recommendations need --fold_in_dataset";
+  if (!FLAGS_user_recommendations.empty() || !FLAGS_fold_in_recommendations.empty())
     CHECK(FLAGS_num_recommendations >= 1 && FLAGS_num_recommendations <= QMFX_REC_MAX_N)
         << "--num_recommendations must be in 1.." << QMFX_REC_MAX_N;
   {
@@ -197,6 +213,20 @@ int main(int argc, char** argv) {
       LOG(INFO) << "timing: similar "
                 << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
                 << " s";
+  }
+  if (!FLAGS_fold_in_dataset.empty()) {
+    LOG(INFO) << "folding in new users";
+    const auto t0 = std::chrono::steady_clock::now();
+    qmf::DatasetReader foldReader(FLAGS_fold_in_dataset);
+    const size_t n = engine.foldInUsers(
+        foldReader.readAll(), FLAGS_fold_in_user_factors, FLAGS_fold_in_recommendations,
+        FLAGS_num_recommendations, FLAGS_recommend_seen,
+        FLAGS_fold_in_epochs > 0 ? FLAGS_fold_in_epochs : FLAGS_nepochs);
+    const char* tm = std::getenv("QMF_TIMINGS");
+    if (tm && std::atoi(tm) > 0)
+      LOG(INFO) << "timing: fold_in "
+                << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                << " s, " << n << " users";
   }
   return 0;
 }
