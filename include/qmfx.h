@@ -102,6 +102,29 @@ int qmfx_fill_uniform(qmfx_ctx* ctx, int side, double bound, uint64_t seed);
  * With a distributed context the local row range is solved and the factor matrix is
  * all-gathered over RCCL before returning; the loss is then the global sum. */
 int qmfx_wals_half(qmfx_ctx* ctx, int side, double alpha, double lambda, double* loss_sum);
+/* The same half by conjugate gradients (opt-in; one device): every row r of `side` with n ≥ 1
+ * signals (column j_e, value v_e; w_e = α·v_e, c_e = 1 + α·v_e, y_j = row j of the other side
+ * as the device holds it) takes `steps` CG steps on A·x = b from its current value,
+ *   A·v = G·v + Σ_e w_e·(y_{j_e}·v)·y_{j_e} + λ·v  (G = YᵀY; A is never formed),  b = Σ_e c_e·y_{j_e}.
+ * Start: x₀ = the row as the context holds it (X is not zeroed; a side never set is all zeros),
+ * r = b − A·x₀, p = r, ρ = r·r.  Step t = 0 .. steps−1: stop if ρ == 0; q = A·p, d = p·q; if
+ * !(d > 0) (NaN included) the row is flagged and stops with its last iterate; a = ρ/d,
+ * x += a·p, r −= a·q, ρ′ = r·r, p = r + (ρ′/ρ)·p, ρ = ρ′.  x is stored in the context
+ * precision.  The row's term of *loss_sum is Σc_e + xᵀ(A−λI)x − 2xᵀb on the stored iterate with
+ * A·x = b − r, written where qmfx_wals_row_losses reads it.  A row without signals is exactly 0
+ * with loss 0.  A flagged row (possible only when some 1 + α·v < 0 or λ ≤ 0) is listed by
+ * qmfx_wals_failed_rows; there is no pivoted re-solve for it.  fp64 contexts compute in double;
+ * fp32 contexts keep the vectors in f32 and accumulate ρ, d and the loss in double.
+ * Rows of the split-K heavy class ([9] of qmfx_row_classes) are solved exactly, as
+ * qmfx_wals_half solves them: they are few, and one wave must not serialise a million gathers
+ * per step.
+ * Fails with -1 before anything is launched when side is not 0 or 1, steps < 1, `side` has no
+ * CSR, the other side has no factors, nfactors > 256, or the context was sharded by
+ * qmfx_dist_init*.  The fixed side, the CSR, the biases and the evaluation state are left as
+ * they are.  The device time and (steps+1)·(2k² + 4nk) flop per CG row (the exact formula for a
+ * heavy row) go into qmfx_solve_kernel_stats. */
+int qmfx_wals_half_cg(qmfx_ctx* ctx, int side, double alpha, double lambda, int steps,
+                      double* loss_sum);
 /* Number of rows whose system the Cholesky kernels could not factor in the last half (a
  * non-positive pivot: some 1 + α·v < 0, λ ≤ 0, or fp32 rounding on a nearly singular
  * system); their indices go to rows[] (up to cap).  qmfx_wals_half has already re-solved

@@ -43,6 +43,7 @@ SIGNATURES = {
     "qmfx_get_factors": [vp, c_int, P_f64],
     "qmfx_fill_uniform": [vp, c_int, c_dbl, c_u64],
     "qmfx_wals_half": [vp, c_int, c_dbl, c_dbl, P_f64],
+    "qmfx_wals_half_cg": [vp, c_int, c_dbl, c_dbl, c_int, P_f64],
     "qmfx_wals_failed_rows": [vp, P_i64, c_i64, P_i64],
     "qmfx_wals_row_losses": [vp, P_f64],
     "qmfx_row_classes": [vp, c_int, P_i64],
@@ -311,6 +312,12 @@ class Context:
     def wals_half(self, side, alpha, lam):
         out = c_dbl(0)
         _check(lib().qmfx_wals_half(self.h, side, alpha, lam, ctypes.byref(out)))
+        return out.value
+
+    def wals_half_cg(self, side, alpha, lam, steps):
+        """One half by `steps` conjugate-gradient steps per row from the side's current factors."""
+        out = c_dbl(0)
+        _check(lib().qmfx_wals_half_cg(self.h, side, alpha, lam, steps, ctypes.byref(out)))
         return out.value
 
     def row_classes(self, side):

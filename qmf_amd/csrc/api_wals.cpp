@@ -10,15 +10,6 @@ using namespace qmfx;
 
 namespace {
 
-int ensure_rowloss(qmfx_ctx* c, int64_t n) {
-  if (c->rowloss_cap >= n) return 0;
-  c->status.reset();
-  HIPCHK(dev_alloc(c->rowloss, (size_t)std::max<int64_t>(n, 1) * sizeof(double)));
-  HIPCHK(dev_alloc(c->status, (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
-  c->rowloss_cap = n;
-  return 0;
-}
-
 ncclDataType_t nccl_type(int prec) { return prec == 32 ? ncclFloat32 : ncclFloat64; }
 
 // G = YᵀY, the whitening and G + λI images, status resets (no collectives)

@@ -168,6 +168,28 @@ hipError_t launch_wals_system(const FallbackArgs<float>& a, int64_t beg, int64_t
 hipError_t launch_wals_system(const FallbackArgs<double>& a, int64_t beg, int64_t end,
                               double* out, hipStream_t s);
 
+// Conjugate-gradient row solves (wals_cg.hip): slots slot_begin .. slot_begin + nslots of the
+// side's order, kCgRows rows per workgroup, `steps` CG steps from each row's current value in X.
+// A row stopped on p·A·p ≤ 0 gets status 1 and keeps its last iterate.
+constexpr int kCgRows = 16;
+constexpr int kCgMaxNT = 16;  // k ≤ 256
+template <typename T>
+struct CgArgs {
+  const int32_t* col;     // indexed with desc.beg (the global rowptr's offsets)
+  const T* val;
+  const T* Y;             // fixed side [nY][kp]
+  const T* G;             // YᵀY of the fixed side, kp×kp
+  T* X;                   // solved side [nX][kp]: in x₀, out x
+  double* rowloss;
+  int32_t* status;        // zero on entry
+  const RowDesc* desc;    // slot → CSR range and row
+  int64_t slot_begin, nslots;
+  T alpha, lambda;
+  int steps;
+};
+hipError_t launch_wals_cg(const CgArgs<float>& a, int nt, hipStream_t s);
+hipError_t launch_wals_cg(const CgArgs<double>& a, int nt, hipStream_t s);
+
 // out[0] = *loss, out[1..2] = fb[0..1], out[3] = *chol (0 when chol is null)
 hipError_t launch_half_status(const double* loss, const unsigned long long* fb,
                               const int32_t* chol, double* out, hipStream_t s);

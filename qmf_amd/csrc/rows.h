@@ -1,5 +1,5 @@
 // Rows solved against a fixed side: the one launch sequence behind a half's pieces
-// (api_wals.cpp) and a fold-in (api_foldin.cpp), what precedes and follows it, and the rows a
+// (api_wals.cpp; the heavy rows of a CG half, api_wals_cg.cpp) and a fold-in (api_foldin.cpp), what precedes and follows it, and the rows a
 // call brings as a CSR of their own (fold-in, qmfx_wals_explain_rows).
 #pragma once
 #include "ctx.h"
@@ -29,6 +29,16 @@ int fixed_side_prologue(qmfx_ctx* c, const SideBuf& R, double lambda, bool use_w
   }
   if (!use_big_rows(c))
     HIPCHK(launch_gimg(c->G.as<const T>(), c->nt, c->k, lambda, c->Gimg.as<T>(), c->stream));
+  return 0;
+}
+
+// the per-row losses and status words of a half over n rows
+inline int ensure_rowloss(qmfx_ctx* c, int64_t n) {
+  if (c->rowloss_cap >= n) return 0;
+  c->status.reset();
+  HIPCHK(dev_alloc(c->rowloss, (size_t)std::max<int64_t>(n, 1) * sizeof(double)));
+  HIPCHK(dev_alloc(c->status, (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
+  c->rowloss_cap = n;
   return 0;
 }
 

@@ -114,6 +114,12 @@ void WALSEngine::reportFailedRows(const int side) {
     count += n;
   }
   if (count == 0) return;
+  if (config_.cgSteps > 0) {
+    // conjugate gradients are defined for positive definite systems only: no re-solve
+    LOG(WARNING) << count << (side == QMFX_USERS ? " user" : " item")
+                 << " systems are not positive definite; stopped at their last iterate";
+    return;
+  }
   // the device re-solved them in fp64 with a pivoted factorization (dsysv_'s role,
   // Matrix.cpp:81-96) inside the half; a singular one fails qmfx_wals_half itself
   LOG(WARNING) << count << (side == QMFX_USERS ? " user" : " item")
@@ -126,6 +132,10 @@ Double WALSEngine::iterate(const int side) {
   if (ranks_.size() > 1)
     QMFX_CHECK(qmfx_wals_half_multi(ranks_.data(), static_cast<int>(ranks_.size()), side,
                                     config_.confidenceWeight, config_.regularizationLambda, &sum));
+  else if (config_.cgSteps > 0)
+    QMFX_CHECK(qmfx_wals_half_cg(dev_->get(), side, config_.confidenceWeight,
+                                 config_.regularizationLambda, static_cast<int>(config_.cgSteps),
+                                 &sum));
   else
     QMFX_CHECK(qmfx_wals_half(dev_->get(), side, config_.confidenceWeight,
                               config_.regularizationLambda, &sum));

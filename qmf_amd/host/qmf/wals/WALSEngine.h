@@ -28,6 +28,9 @@ struct WALSConfig {
   Double confidenceWeight;
   Double initDistributionBound;
   std::string DistributionFile;
+  // 0: every row is solved exactly; N > 0: N warm-started conjugate-gradient steps per row
+  // and half (qmfx_wals_half_cg; one device)
+  size_t cgSteps = 0;
 };
 
 class WALSEngine : public Engine {

@@ -1,5 +1,6 @@
 // `wals` command line, drop-in for the reference's qmf/wals.cpp:26-107: same flags, same
-// log lines and output files.  Additions: --device, --precision (32 | 64), --ngpus, and the
+// log lines and output files.  Additions: --device, --precision (32 | 64), --ngpus,
+// --solver=exact|cg with --cg_steps (conjugate-gradient row solves, one GPU), and the
 // top-N recommendations of the trained model: --user_recommendations, --num_recommendations,
 // --recommend_seen, --recommend_users, and one of --recommend_exclude_items FILE (item ids never
 // recommended), --recommend_items FILE (the only item ids recommended) or
@@ -36,6 +37,10 @@ DEFINE_double(regularization_lambda, 0.05, "regularization param");
 DEFINE_double(confidence_weight, 40, "confidence weight");
 DEFINE_double(init_distribution_bound, 0.01, "init distirbution bound");
 DEFINE_string(distribution_file, "", "uniform distribution file, for repeatable result");
+DEFINE_string(solver, "exact",
+              "row solves: exact (factorization, the reference's) or cg (--cg_steps warm-started "
+              "conjugate-gradient steps per row and half; one GPU)");
+DEFINE_int32(cg_steps, 3, "conjugate-gradient steps per row and half with --solver=cg");
 // settings
 DEFINE_int32(nthreads, 16, "number of host threads (ingest, evaluation, output)");
 DEFINE_int32(device, qmf::DeviceOptions::envInt("QMF_DEVICE", 0), "GPU ordinal");
@@ -116,12 +121,16 @@ int main(int argc, char** argv) {
   if (FLAGS_user_factors.empty() || FLAGS_item_factors.empty()) {
     LOG(WARNING) << "warning: missing model output filenames! (use options --{user,item}_factors)";
   }
+  CHECK(FLAGS_solver == "exact" || FLAGS_solver == "cg") << "--solver must be exact or cg";
+  CHECK(FLAGS_cg_steps >= 1) << "--cg_steps must be at least 1";
+  CHECK(FLAGS_solver != "cg" || FLAGS_ngpus <= 1) << "--solver=cg runs on one GPU (--ngpus 1)";
   qmf::WALSConfig config{FLAGS_nepochs,
                          FLAGS_nfactors,
                          FLAGS_regularization_lambda,
                          FLAGS_confidence_weight,
                          FLAGS_init_distribution_bound,
-                         FLAGS_distribution_file};
+                         FLAGS_distribution_file,
+                         FLAGS_solver == "cg" ? static_cast<size_t>(FLAGS_cg_steps) : 0};
   qmf::MetricsConfig metricsConfig{FLAGS_num_test_users, FLAGS_test_always, FLAGS_eval_seed};
   const auto metricsEngine = std::make_unique<qmf::MetricsEngine>(metricsConfig);
   for (const auto& metric : qmf::split(FLAGS_test_avg_metrics, ',')) {
